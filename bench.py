@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """bench.py — decode-step throughput of the hot path on MI355X, Llama-3-8B GPTQ-int4 (Marlin format) TP=1.
 
-Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0).
+Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (rank 0). Such a plain run sets up, warms up,
+times the K steps and prints the headline (`value`, `ms_per_step`); everything that takes runs of its own - `roofline` /
+`rooflines` / `kernels`, `allreduce`, `cpu_baseline` - is measured and added to the line only with `--full`.
   step      = one decode step of the whole batch through 32 decoder layers + lm_head:
               per layer RMSNorm -> int4 qkv GEMM -> RoPE -> reshape_and_cache -> paged_attention -> int4 o_proj GEMM
               -> RMSNorm(+residual) -> int4 gate_up GEMM -> SiLU*mul -> int4 down GEMM; then final norm, fp16 lm_head,
@@ -16,9 +18,10 @@ Contract: `python bench.py --gpus N --steps K --warmup W` prints ONE JSON line (
   --tp N    : ONE model sharded over the N ranks (Megatron TP, config 5: Llama-3-70B AWQ TP=8): column-parallel qkv /
               gate_up, row-parallel o / down, each followed by an RCCL all-reduce of [batch, hidden] fp16 INSIDE the
               captured step (linear.py:791-793 -> parallel_state.py:273-293); value = tokens/s of the whole job (strong).
-  roofline  = the quantized-GEMM kernel class (what the metric names), timed with HIP events on the launch stream;
-              rooflines = that class and paged attention.
-  cpu_baseline = the CPU oracle (a port: dequant + fp32 matmul, scalar attention) on a bounded sample, rank 0 only.
+  --dump-outputs DIR : after the timed steps, what the last of them computed goes to DIR/<name>.npy (dump_outputs()).
+  roofline  = (--full) the quantized-GEMM kernel class (what the metric names), timed with HIP events on the launch
+              stream; rooflines = that class and paged attention.
+  cpu_baseline = (--full) the CPU oracle (a port: dequant + fp32 matmul, scalar attention) on a bounded sample, rank 0 only.
 Synthetic data: random token ids / activations, random-init int4 weights of the Llama-3-8B shapes.
 """
 import argparse
@@ -107,16 +110,28 @@ def parse():
                     "norm-fused GEMM prologue at batch <= 4)")
     ap.add_argument("--no-attn-absmax", action="store_true", help="fp8: separate absmax pass over the attention output (A/B of paged_attention_v1/v2_absmax)")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what is not part of the headline, each in runs of its own "
+                    "after the timed steps: per-kernel timings and rooflines, the all-reduce chain of --tp, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without its CPU baseline")
     ap.add_argument("--sweep", action="store_true", help="also report batch 1/8/64/256 decode and the int4 GEMM TFLOP/s table")
     return ap.parse_args()
+
+
+def random_scales(K, N, group, device, gen):
+    """Group scales [K/group, N] fp16 of the random-init int4 weights, 0.0005 .. 0.0015. Random int4 codes have a mean of
+    -0.5, so every linear layer adds a component common to all its outputs, and the fp16 residual stream gathers the down
+    projection's, which grows with the cube of the scales (gate_up, its activation product, down): with 0.002 .. 0.006 it went
+    by -1430 per layer and left fp16's range (65504) in the last of the 32 layers, NaN logits in 12 of 256 rows. A quarter
+    of those scales leaves a factor of 64 per layer; the kernels' work does not depend on the values."""
+    return (torch.rand(K // group, N, device=device, generator=gen) * 0.001 + 0.0005).to(torch.float16)
 
 
 def random_marlin_weight(K, N, group, device, gen):
     """Random-init int4 weight already in Marlin layout: any int32 word is a valid packed tile row
     ([K/16, N*16/8]); scales [K/group, N] fp16 (Marlin-permuted order is irrelevant for random values)."""
     q = torch.randint(-2**31, 2**31 - 1, (K // 16, N * 2), dtype=torch.int32, device=device, generator=gen)
-    s = (torch.rand(K // group, N, device=device, generator=gen) * 0.004 + 0.002).to(torch.float16)
+    s = random_scales(K, N, group, device, gen)
     return q, s
 
 
@@ -124,7 +139,7 @@ def random_weight(variant, K, N, group, device, gen):
     """Random-init weights of one linear layer in the layout the variant's op consumes."""
     if variant == "int4":
         return random_marlin_weight(K, N, group, device, gen)
-    s = (torch.rand(K // group, N, device=device, generator=gen) * 0.004 + 0.002).to(torch.float16)
+    s = random_scales(K, N, group, device, gen)
     if variant == "sparse24":
         # compressed non-zeros [K/2/16, N*16/8] + 2-bit positions [K/32, 2N] int16: every quad keeps elements 0 and 1
         # (nibble 0b0100) - a valid encoding; which positions are kept does not change the work
@@ -222,6 +237,7 @@ class Llama3Decode:
             self.exp_sums = torch.empty(batch, nh, self.P, dtype=torch.float32, device=device)
             self.max_logits = torch.empty(batch, nh, self.P, dtype=torch.float32, device=device)
         self.next_tokens = torch.zeros(batch, dtype=torch.long, device=device)
+        self.logits = None  # [batch, vocab] of the last step (in a replayed graph: the capture's buffer); read by dump_outputs()
 
     def gemm_as_in_step(self, x, w, name):
         """The GEMM launch the captured step issues for this layer: with fused consumers (the default) the deferred form - the
@@ -350,6 +366,7 @@ class Llama3Decode:
         logits = torch.matmul(x, self.lm_head.t())
         if self.all_gather is not None:
             logits = self.all_gather(logits)
+        self.logits = logits
         self.next_tokens.copy_(logits.argmax(-1))
         return self.next_tokens
 
@@ -386,6 +403,7 @@ class Llama3Decode:
             nxt = self.layers[li + 1]["ln1"] if li + 1 < self.n_layers else self.final_ln
             x, amax = ops.fused_add_rms_norm_splitk(mm(act, amax, lw["down"]), resid, nxt, 1e-5, want_absmax=True)
         logits = torch.matmul(x, self.lm_head.t())
+        self.logits = logits
         self.next_tokens.copy_(logits.argmax(-1))
         return self.next_tokens
 
@@ -428,6 +446,7 @@ class Llama3Decode:
         logits = torch.matmul(h, self.lm_head.t())
         if self.all_gather is not None:
             logits = self.all_gather(logits)  # vocab-parallel lm_head (logits_processor.py: gather of the shards)
+        self.logits = logits
         self.next_tokens.copy_(logits.argmax(-1))
         return self.next_tokens
 
@@ -577,6 +596,30 @@ def pmc_traffic(kernels, args):
         return None, None
 
 
+DUMP_LOGITS_BYTES = 48 << 20  # of the 64 MB a dump may take
+
+
+def dump_outputs(model, out_dir):
+    """--dump-outputs: what the last timed step handed to its caller, as .npy files for comparing two builds output for
+    output (weights, KV cache and token ids come from seeded generators, so the same arguments give the same inputs).
+      next_tokens.npy [batch] float64: the greedy token ids the step returns (exact in float64)
+      logits.npy [batch, n] float32: the logits the argmax was taken over - the ids of random-init weights flip on a
+        last-bit change, the logits show its size. Beyond DUMP_LOGITS_BYTES a fixed (seeded) sorted sample of the vocabulary
+        columns, the same in every run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    logits = model.logits
+    rows, cols = logits.shape
+    keep = max(1, DUMP_LOGITS_BYTES // (4 * rows))
+    if keep < cols:
+        g = torch.Generator()
+        g.manual_seed(0)
+        idx = torch.randperm(cols, generator=g)[:keep].sort().values
+        logits = logits[:, idx.to(logits.device)]
+    np.save(os.path.join(out_dir, "next_tokens.npy"), model.next_tokens.cpu().numpy().astype(np.float64))
+    np.save(os.path.join(out_dir, "logits.npy"), logits.float().cpu().numpy())
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start the N ranks as children (this parent never touches a GPU -
     nothing here may exec or re-exec a process that has initialised one) and relay rank 0's JSON line."""
@@ -602,6 +645,64 @@ def spawn_ranks(args):
     sys.stdout.write(out.decode())
     sys.stdout.flush()
     return max(abs(rc) for rc in rcs)
+
+
+def kernel_report(model, args, ms_per_step):
+    """--full: the result line's `roofline` / `rooflines` / `kernels` / `hot_path_share_of_step`, from timed runs of every
+    kernel class of the step on its own (kernel_breakdown)."""
+    kb = kernel_breakdown(model)
+    per_step = {k: v["ms"] * v["launches"] for k, v in kb.items()}
+    # kernel classes: the four int4 GEMM launches of a layer are one kernel (marlin_gemm_kernel [+ its split-K reduce]);
+    # per-launch figures are the mean over the four shapes, which is what rocprofv3's per-kernel average reports too.
+    gem = [v for k, v in kb.items() if "_gemm_" in k]
+    # int4: the class is named after the kernel that serves most of its launches at this batch (rows > 64: the wide /
+    # ring kernels of marlin_wide.hip, else the row-block kernel); every kernel of the class is listed for the PMC sums
+    int4_names = ("marlin_wide_kernel", "marlin_gemm_kernel") if args.batch > 64 else ("marlin_gemm_kernel", "marlin_wide_kernel")
+    gemm_kernels = {"int4": int4_names + ("marlin_dma_kernel", "marlin_decode_kernel"),
+                    "sparse24": ("marlin_gemm_kernel", "splitk_reduce_kernel"),
+                    "fp8": ("scaled_mm_kernel", ),
+                    "gptq-exllama": ("gptq_gemm_kernel", "splitk_reduce_kernel"),
+                    "awq70b": ("marlin_gemm_kernel", "awq_gemm_kernel", "splitk_reduce_kernel"),
+                    "awq70b-tp8rank": ("marlin_gemm_kernel", "awq_gemm_kernel", "splitk_reduce_kernel")}[args.config]
+    att = [v for k, v in kb.items() if k.startswith("paged_attention")][0]
+    gem_ms = sum(v["ms"] for v in gem)
+    classes = {
+        gemm_kernels[0]: dict(ms=gem_ms / len(gem), bytes=sum(v["bytes"] for v in gem) / len(gem),
+                              flops=sum(v["flops"] for v in gem) / len(gem), step_ms=gem_ms * gem[0]["launches"],
+                              prof=gemm_kernels),
+        "paged_attention_kernel": dict(ms=att["ms"], bytes=att["bytes"], flops=att["flops"],
+                                       step_ms=att["ms"] * att["launches"], prof=("paged_attention_kernel", )),
+    }
+    def roof_of(name):
+        d = classes[name]
+        d["gbs"] = d["bytes"] / d["ms"] / 1e6
+        d["tflops"] = d["flops"] / d["ms"] / 1e9
+        mfma_peak = MFMA_F16_PEAK_TF * (2.0 if (args.config == "fp8" and name != "paged_attention_kernel") else 1.0)  # fp8: 5 PF
+        # HBM-bound below the ridge (4*M flop/B vs ~312 flop/B machine balance)
+        hbm_bound = d["flops"] / d["bytes"] < mfma_peak * 1e12 / (HBM_PEAK_GBS * 1e9)
+        traffic, traffic_src = pmc_traffic(d["prof"], args)
+        common = dict(kernel=name, traffic=traffic, traffic_source=traffic_src, avg_launch_us=round(d["ms"] * 1e3, 2),
+                      step_share_ms=round(d["step_ms"], 3), kernels_in_launch=list(d["prof"]))
+        if hbm_bound:
+            return dict(bound="hbm", achieved=round(d["gbs"], 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                        frac=round(d["gbs"] / HBM_PEAK_GBS, 4), algorithmic_bytes_per_launch=int(d["bytes"]), **common)
+        return dict(bound="mfma", achieved=round(d["tflops"], 1), peak=mfma_peak, unit="TFLOP/s",
+                    frac=round(d["tflops"] / mfma_peak, 4), algorithmic_flops_per_launch=float(d["flops"]),
+                    algorithmic_bytes_per_launch=int(d["bytes"]),
+                    traffic_over_algorithmic=(round(traffic / d["bytes"], 3) if traffic else None), **common)
+
+    rooflines = {name: roof_of(name) for name in classes}
+    # `roofline` = the kernel class the metric names: BASELINE.json's metric is "decode tokens/sec + int4 GEMM TFLOPS vs
+    # roofline", so the quantized-GEMM class is reported whatever its share of the step (VERDICT r02 item 3: at batch
+    # 256 paged attention has the larger share and used to take this slot); `rooflines` carries both classes
+    roof = rooflines[gemm_kernels[0]]
+    return {
+        "roofline": roof,
+        "rooflines": rooflines,
+        "kernels": {k: {"us": round(v["ms"] * 1e3, 2), "GBps": round(v["gbs"], 1), "TFLOPs": round(v["tflops"], 2),
+                        "step_share_ms": round(per_step[k], 3)} for k, v in kb.items()},
+        "hot_path_share_of_step": round(sum(per_step.values()) / ms_per_step, 3),
+    }
 
 
 def main():
@@ -696,8 +797,10 @@ def main():
     ms_per_step = dt / args.steps * 1e3
     replicas = 1 if tp > 0 else world
     value = replicas * args.batch * args.steps / dt
+    if args.dump_outputs and rank == 0:
+        dump_outputs(model, args.dump_outputs)
     ar_stats = None
-    if tp > 0:
+    if tp > 0 and args.full:
         # the step's all-reduce on its own: 2 per layer of [batch, hidden] fp16, chained in one graph
         buf = torch.randn(args.batch, cfg["hidden"], device=dev, dtype=torch.float16)
         n_ar = 2 * args.layers
@@ -716,52 +819,6 @@ def main():
 
     result = None
     if rank == 0:
-        kb = kernel_breakdown(model)
-        per_step = {k: v["ms"] * v["launches"] for k, v in kb.items()}
-        # kernel classes: the four int4 GEMM launches of a layer are one kernel (marlin_gemm_kernel [+ its split-K reduce]);
-        # per-launch figures are the mean over the four shapes, which is what rocprofv3's per-kernel average reports too.
-        gem = [v for k, v in kb.items() if "_gemm_" in k]
-        # int4: the class is named after the kernel that serves most of its launches at this batch (rows > 64: the wide /
-        # ring kernels of marlin_wide.hip, else the row-block kernel); every kernel of the class is listed for the PMC sums
-        int4_names = ("marlin_wide_kernel", "marlin_gemm_kernel") if args.batch > 64 else ("marlin_gemm_kernel", "marlin_wide_kernel")
-        gemm_kernels = {"int4": int4_names + ("marlin_dma_kernel", "marlin_decode_kernel"),
-                        "sparse24": ("marlin_gemm_kernel", "splitk_reduce_kernel"),
-                        "fp8": ("scaled_mm_kernel", ),
-                        "gptq-exllama": ("gptq_gemm_kernel", "splitk_reduce_kernel"),
-                        "awq70b": ("marlin_gemm_kernel", "awq_gemm_kernel", "splitk_reduce_kernel"),
-                        "awq70b-tp8rank": ("marlin_gemm_kernel", "awq_gemm_kernel", "splitk_reduce_kernel")}[args.config]
-        att = [v for k, v in kb.items() if k.startswith("paged_attention")][0]
-        gem_ms = sum(v["ms"] for v in gem)
-        classes = {
-            gemm_kernels[0]: dict(ms=gem_ms / len(gem), bytes=sum(v["bytes"] for v in gem) / len(gem),
-                                  flops=sum(v["flops"] for v in gem) / len(gem), step_ms=gem_ms * gem[0]["launches"],
-                                  prof=gemm_kernels),
-            "paged_attention_kernel": dict(ms=att["ms"], bytes=att["bytes"], flops=att["flops"],
-                                           step_ms=att["ms"] * att["launches"], prof=("paged_attention_kernel", )),
-        }
-        def roof_of(name):
-            d = classes[name]
-            d["gbs"] = d["bytes"] / d["ms"] / 1e6
-            d["tflops"] = d["flops"] / d["ms"] / 1e9
-            mfma_peak = MFMA_F16_PEAK_TF * (2.0 if (args.config == "fp8" and name != "paged_attention_kernel") else 1.0)  # fp8: 5 PF
-            # HBM-bound below the ridge (4*M flop/B vs ~312 flop/B machine balance)
-            hbm_bound = d["flops"] / d["bytes"] < mfma_peak * 1e12 / (HBM_PEAK_GBS * 1e9)
-            traffic, traffic_src = pmc_traffic(d["prof"], args)
-            common = dict(kernel=name, traffic=traffic, traffic_source=traffic_src, avg_launch_us=round(d["ms"] * 1e3, 2),
-                          step_share_ms=round(d["step_ms"], 3), kernels_in_launch=list(d["prof"]))
-            if hbm_bound:
-                return dict(bound="hbm", achieved=round(d["gbs"], 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                            frac=round(d["gbs"] / HBM_PEAK_GBS, 4), algorithmic_bytes_per_launch=int(d["bytes"]), **common)
-            return dict(bound="mfma", achieved=round(d["tflops"], 1), peak=mfma_peak, unit="TFLOP/s",
-                        frac=round(d["tflops"] / mfma_peak, 4), algorithmic_flops_per_launch=float(d["flops"]),
-                        algorithmic_bytes_per_launch=int(d["bytes"]),
-                        traffic_over_algorithmic=(round(traffic / d["bytes"], 3) if traffic else None), **common)
-
-        rooflines = {name: roof_of(name) for name in classes}
-        # `roofline` = the kernel class the metric names: BASELINE.json's metric is "decode tokens/sec + int4 GEMM TFLOPS vs
-        # roofline", so the quantized-GEMM class is reported whatever its share of the step (at batch
-        # 256 paged attention has the larger share and used to take this slot); `rooflines` carries both classes
-        roof = rooflines[gemm_kernels[0]]
         result = {
             "metric": var["metric"],
             "value": round(value, 1),
@@ -781,17 +838,15 @@ def main():
                        "fused_consumers": bool(model.fuse),
                        "parallelism": (f"tp{tp} (one model over {tp} ranks, RCCL all-reduce in the captured step)" if tp > 0
                                        else f"dp{world} (independent TP=1 replicas)")},
-            "roofline": roof,
-            "rooflines": rooflines,
-            "kernels": {k: {"us": round(v["ms"] * 1e3, 2), "GBps": round(v["gbs"], 1), "TFLOPs": round(v["tflops"], 2),
-                            "step_share_ms": round(per_step[k], 3)} for k, v in kb.items()},
-            "hot_path_share_of_step": round(sum(per_step.values()) / ms_per_step, 3),
         }
+        if args.full:
+            result.update(kernel_report(model, args, ms_per_step))
         if tp > 0:
             result["tp"] = tp
-            result["allreduce"] = ar_stats
+            if args.full:
+                result["allreduce"] = ar_stats
             # the communicator as torch.distributed / RCCL see it: ranks in the default group that
-            # carried the all-reduces above, the backend name and the RCCL version linked into torch
+            # carried the step's all-reduces, the backend name and the RCCL version linked into torch
             try:
                 ver = ".".join(str(v) for v in torch.cuda.nccl.version())
             except Exception:
@@ -800,7 +855,7 @@ def main():
                               "rank0_device": str(dev)}
         if args.sweep and args.config == "int4":
             result["sweep"] = sweep(ops, cfg, dev)
-        if not args.no_cpu_baseline and args.config == "int4" and world == 1:  # headline workload, single-GPU run only
+        if args.full and not args.no_cpu_baseline and args.config == "int4" and world == 1:  # headline workload, single-GPU run only
             result["cpu_baseline"] = cpu_baseline(cfg, args.batch, args.ctx)
         print(json.dumps(result), flush=True)
     if dist is not None:

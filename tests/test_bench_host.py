@@ -20,6 +20,31 @@ def test_gpus_flag_without_gpus_reports_and_fails():
     assert "error" in rec and rec["n_gpus"] == 0
 
 
+def test_dump_outputs_samples_large_logits(tmp_path, monkeypatch):
+    """--dump-outputs: float64 token ids and float32 logits; past the byte budget the same sorted sample of columns in
+    every call, so two dumps of equal outputs are equal files."""
+    import types
+
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(bench, "DUMP_LOGITS_BYTES", 3 * 4 * 5)  # 5 of the 11 columns of 3 rows
+    logits = torch.arange(33, dtype=torch.float16).reshape(3, 11)
+    model = types.SimpleNamespace(logits=logits, next_tokens=torch.tensor([10, 10, 10]))
+    bench.dump_outputs(model, str(tmp_path / "a"))
+    bench.dump_outputs(model, str(tmp_path / "b"))
+    tok, lg = np.load(tmp_path / "a" / "next_tokens.npy"), np.load(tmp_path / "a" / "logits.npy")
+    assert tok.dtype == np.float64 and tok.tolist() == [10.0, 10.0, 10.0]
+    assert lg.dtype == np.float32 and lg.shape == (3, 5)
+    cols = lg[0].astype(np.int64)  # row 0 holds the column numbers
+    assert (np.diff(cols) > 0).all() and np.array_equal(lg, logits.float().numpy()[:, cols])
+    assert np.array_equal(lg, np.load(tmp_path / "b" / "logits.npy"))
+    monkeypatch.setattr(bench, "DUMP_LOGITS_BYTES", 3 * 4 * 11)  # fits: every column, in place
+    bench.dump_outputs(model, str(tmp_path / "c"))
+    assert np.array_equal(np.load(tmp_path / "c" / "logits.npy"), logits.float().numpy())
+
+
 def test_tp_shard_of_llama3_70b():
     sys.path.insert(0, ROOT)
     import bench

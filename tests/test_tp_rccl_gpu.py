@@ -91,7 +91,7 @@ def test_bench_tp_mode_one_rank():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "awq70b", "--tp", "1", "--gpus", "1",
-                          "--layers", "2", "--batch", "8", "--ctx", "128", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"],
+                          "--layers", "2", "--batch", "8", "--ctx", "128", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"],
                          env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]

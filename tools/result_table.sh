@@ -6,7 +6,7 @@ out=$root/gpurun_out/results_$1.txt
 : > $out
 run() {
   cfg=$1; b=$2; shift 2
-  timeout -k 10 300 python3 $root/bench.py --config $cfg --batch $b --steps 10 --no-cpu-baseline "$@" > /tmp/rt.log 2>&1
+  timeout -k 10 300 python3 $root/bench.py --config $cfg --batch $b --steps 10 --full --no-cpu-baseline "$@" > /tmp/rt.log 2>&1
   python3 - "$cfg $*" $b >> $out <<'PY'
 import json, sys
 ln = [l for l in open("/tmp/rt.log") if l.startswith("{")]
