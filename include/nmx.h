@@ -314,6 +314,36 @@ int nmx_awq_marlin_gemm_deferred(const void* a, const int32_t* q, const void* sc
                                  void* scratch, int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups,
                                  int* splits_out, nmx_stream_t stream);
 
+/* CDNA4-native W4A16 (no reference counterpart: the reference repacks GPTQ checkpoints into Marlin's order - the fragment order
+ * of NVIDIA's mma.m16n8k16 - at load, gptq_marlin.py:330-420; this is the same one-time repack into the order gfx950's
+ * v_mfma_f32_16x16x32_{f16,bf16} consumes with the weights as its A operand and natural-k activations as B). 4-bit symmetric,
+ * fp16 / bf16, size_k % 128 == 0, size_n % 64 == 0, one scale group per column or per 128 k, no act-order:
+ * nmx_w4a16_supported() answers for a layer; everything else stays on the Marlin entries. The layout (the contract):
+ *   qweight_native  int32 [size_k / 128, size_n * 16], element order [u = k / 128][c = n / 64][s][lane l = 16 g + r][t]:
+ *     word (u, c, s, l, t) holds the 8 codes of column n = 64 c + 16 t + r at k = 128 u + 32 s + 8 g + j, j = 0 .. 7, code j in
+ *     nibble P[j], P = [0, 4, 1, 5, 2, 6, 3, 7] - (w & 0x000f000f), (w & 0x00f000f0) and the same two masks on w >> 8 yield the
+ *     half2 pairs (k0,k1) (k2,k3) (k4,k5) (k6,k7) in fragment order. A lane's 16-byte load = the A-fragment words of its wave's
+ *     four 16-column tiles for one 32-k step; a wave reads 4 KiB contiguous per 128-k unit. size_k * size_n / 8 words.
+ *   scales_native   scalar dtype [num_groups, size_n], element order [G][c = n / 64][g][t][j], n = 64 c + 16 t + 4 g + j: the 16
+ *     scales of a lane's accumulators (D rows 4 g + j of its four tiles) are 32 contiguous bytes.
+ * c = a * W with W[k, n] = (q - 8) * s[group(k), n]: q - 8 is converted exactly, products are summed in fp32 per 128-k group and
+ * the group's sum is multiplied by s in fp32.
+ * nmx_w4a16_repack: GPTQ checkpoint qweight [size_k / 8, size_n] int32 (packed along K, sequential nibbles) + scales
+ * [num_groups, size_n] -> the native pair, one launch; qzeros is not read (symmetric format).
+ * nmx_w4a16_gemm_scratch_bytes: bytes of fp32 split-K slabs the dispatch can use (0: no split). The GEMM uses fewer splits with less.
+ * nmx_w4a16_gemm_deferred: as nmx_gptq_marlin_gemm_deferred - with *splits_out > 1 the fp32 slabs [*splits_out, size_m, size_n]
+ * are left at the start of scratch for nmx_splitk_reduce or a *_splitk consumer and c is untouched. size_m is free (row blocks
+ * of 64 above 64 rows). All entries only enqueue. */
+int nmx_w4a16_supported(int size_n, int size_k, int num_groups, int num_bits, int has_act_order);
+int nmx_w4a16_repack(const int32_t* qweight, const void* scales, int32_t* qweight_native, void* scales_native, int size_k,
+                     int size_n, int num_groups, int dtype, nmx_stream_t stream);
+int64_t nmx_w4a16_gemm_scratch_bytes(int size_m, int size_n, int size_k);
+int nmx_w4a16_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                   int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, nmx_stream_t stream);
+int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                            int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int* splits_out,
+                            nmx_stream_t stream);
+
 /* marlin_gemm (csrc/quantization/marlin/dense/marlin_cuda_kernel.cu:1045-1136): int4, fp16, groups of 128 or
  * channel-wise, weights Marlin-packed in the checkpoint. */
 int nmx_marlin_gemm(const void* a, const int32_t* b_q_weight, const void* b_scales, void* c,

@@ -26,7 +26,8 @@ def lib() -> ctypes.CDLL:
         _lib = ctypes.CDLL(LIB_PATH)
         _lib.nmx_last_error.restype = ctypes.c_char_p
         _lib.nmx_version.restype = ctypes.c_char_p
-        for fn in ("nmx_marlin_gemm_scratch_bytes", "nmx_zp_gemm_scratch_bytes", "nmx_scaled_mm_scratch_bytes"):
+        for fn in ("nmx_marlin_gemm_scratch_bytes", "nmx_zp_gemm_scratch_bytes", "nmx_scaled_mm_scratch_bytes",
+                   "nmx_w4a16_gemm_scratch_bytes"):
             getattr(_lib, fn).restype = ctypes.c_int64
         _lib.nmx_tuning_set.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     return _lib

@@ -1,0 +1,484 @@
+// W4A16 on a weight layout made for gfx950 (include/nmx.h "CDNA4-native W4A16"): the GPTQ checkpoint tensors
+// are rewritten ONCE into the order v_mfma_f32_16x16x32_{f16,bf16} consumes with the WEIGHTS as its A operand and natural-k
+// activations as B, and the GEMM streams that order with one 16-byte load per lane and 32-k step. No reference counterpart (the
+// reference repacks GPTQ -> Marlin at load, gptq_marlin.py:330-420, into the fragment order of NVIDIA's mma.m16n8k16).
+//
+//   qweight_native  int32 [K / 128][N / 64][step s = 0..3][lane l = 16 g + r][tile t = 0..3]
+//       word (u, c, s, l, t) = the 8 codes of column n = 64 c + 16 t + r at k = 128 u + 32 s + 8 g + j, code j in nibble
+//       P[j] = [0, 4, 1, 5, 2, 6, 3, 7]: (w & 0x000f000f), (w & 0x00f000f0) and the same masks on w >> 8 are the fp16 pairs
+//       (k0,k1) (k2,k3) (k4,k5) (k6,k7) of the lane's A fragment. A lane's 16 bytes = its fragment words of the wave's four
+//       16-column tiles for ONE 32-k step, so the register is free - and re-issued two units ahead - right after that step.
+//   scales_native   scalar [G][N / 64][g][t][j] = scales[G][64 c + 16 t + 4 g + j]: the 16 scales of a lane's accumulators
+//       (D row 4 g + j of tile t) are 32 contiguous bytes. The scales multiply the fp32 accumulators of a 128-k unit, not the
+//       weights: (q - 8) * s cannot be formed by one fp16 FMA on the magic-number form (the addend -1032 s needs 19 bits).
+#include "nmx_common.h"
+
+#include <stdlib.h>
+
+namespace {
+
+struct W4Params {
+  const void* a;          // [M, K]
+  const int32_t* qw;      // qweight_native
+  const void* scales;     // scales_native
+  void* c;                // [M, N]
+  float* partial;         // [k_splits, M, N] fp32 slabs (k_splits > 1)
+  int M, N, K, num_groups, k_splits;
+  int xcd_per;            // > 0: XCDs per K split (2 / 4 / 8 splits, the split is chosen by the workgroup id % 8)
+};
+
+struct W4Cfg { int mt, nw, splits; };
+
+template <typename scalar_t>
+__device__ __forceinline__ f32x4 mfma_w4(u32x4 a, u32x4 b, f32x4 c) {
+  if constexpr (__is_same(scalar_t, f16))
+    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
+  else
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// (q & mask) | magic as ONE v_and_or_b32 (mask in an SGPR, magic in a VGPR: a VOP3 cannot carry two literals)
+__device__ __forceinline__ uint32_t and_or_w4(uint32_t q, uint32_t mask, uint32_t magic) {
+  uint32_t r;
+  asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(q), "s"(mask), "v"(magic));
+  return r;
+}
+
+// One packed word -> the lane's A fragment (8 values q - 8, exact). fp16: 1 shift + 4 v_and_or_b32 + 2 v_pk_add_f16 + 2 v_pk_fma_f16
+// = 9 VALU (1024 + q - 1032; (1024 + 16 q) / 16 - 72). bf16 has no packed arithmetic on gfx950: every code goes through fp32
+// (128 + q as the float 0x4300'0000 | q << 16, minus 136), then v_cvt_pk_bf16_f32 per pair.
+template <typename scalar_t>
+__device__ __forceinline__ u32x4 w4_fragment(uint32_t w, uint32_t magic) {
+  if constexpr (__is_same(scalar_t, f16)) {
+    const f16x2 sub = __builtin_bit_cast(f16x2, 0x64086408u), r16 = __builtin_bit_cast(f16x2, 0x2c002c00u),
+                n72 = __builtin_bit_cast(f16x2, 0xd480d480u);
+    const uint32_t w8 = w >> 8;
+    const f16x2 p0 = __builtin_bit_cast(f16x2, and_or_w4(w, 0x000f000fu, magic)) - sub;
+    const f16x2 p1 = __builtin_bit_cast(f16x2, and_or_w4(w, 0x00f000f0u, magic)) * r16 + n72;
+    const f16x2 p2 = __builtin_bit_cast(f16x2, and_or_w4(w8, 0x000f000fu, magic)) - sub;
+    const f16x2 p3 = __builtin_bit_cast(f16x2, and_or_w4(w8, 0x00f000f0u, magic)) * r16 + n72;
+    return u32x4{__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1), __builtin_bit_cast(uint32_t, p2),
+                 __builtin_bit_cast(uint32_t, p3)};
+  } else {
+    u32x4 o;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {  // pair i = codes 2 i, 2 i + 1 = nibbles i, i + 4
+      const float lo = __builtin_bit_cast(float, ((w << (16 - 4 * i)) & 0x000f0000u) | 0x43000000u) - 136.f;
+      const float hi = __builtin_bit_cast(float, ((w >> (4 * i)) & 0x000f0000u) | 0x43000000u) - 136.f;
+      union { bf16 h[2]; uint32_t u; } pk;
+      pk.h[0] = (bf16)lo;
+      pk.h[1] = (bf16)hi;
+      o[i] = pk.u;
+    }
+    return o;
+  }
+}
+
+// ---- repack: GPTQ checkpoint qweight [K / 8, N] (code k % 8 of row k / 8 at bits 4 (k % 8)) + scales [G, N] -> the native pair.
+// Native word (u, c, s, 16 g + r, t) is checkpoint word (16 u + 4 s + g, 64 c + 16 t + r) with its nibbles moved j -> P[j].
+__global__ void w4a16_repack_kernel(const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
+                                    uint32_t* __restrict__ qnative, uint16_t* __restrict__ snative, int K, int N, int G) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t words = (int64_t)(K / 8) * N;
+  const int C = N / 64;
+  if (o < words) {
+    const int t = (int)(o & 3), l = (int)(o >> 2) & 63, s = (int)(o >> 8) & 3;
+    const int64_t uc = o >> 10;
+    const int c = (int)(uc % C), u = (int)(uc / C);
+    const int kk = 16 * u + 4 * s + (l >> 4), n = 64 * c + 16 * t + (l & 15);
+    const uint32_t w = qweight[(int64_t)kk * N + n];
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r |= ((w >> (4 * j)) & 0xfu) << (4 * ((j >> 1) + 4 * (j & 1)));
+    qnative[o] = r;
+  }
+  if (o < (int64_t)G * N) {
+    const int j = (int)(o & 3), t = (int)(o >> 2) & 3, g = (int)(o >> 4) & 3;
+    const int64_t gc = o >> 6;
+    const int c = (int)(gc % C), grp = (int)(gc / C);
+    snative[o] = scales[(int64_t)grp * N + 64 * c + 16 * t + 4 * g + j];
+  }
+}
+
+// ---- the GEMM. c [M, N] = a [M, K] . W, W[k, n] = (q - 8) * s[group(k), n].
+// D = W^T-tile (A operand, 16 columns x 32 k) x activations (B operand, 32 k x 16 rows): lane (g, r) of tile t holds rows
+// m = r, columns 16 t + 4 g + 0..3 - four consecutive outputs, one 8-byte store.
+//   STAGED = false (MT = 1, up to 16 rows): NW waves on ONE 64-column group, every wave its own K slice in units of 128 k; a
+//     lane's B fragment is 16 contiguous bytes of its activation row straight from global memory, no LDS and no barrier in the
+//     loop; the NW slices are summed through LDS with one barrier.
+//   STAGED = true (MT = 2 / 4): 4 waves on 4 ADJACENT column groups sharing one K slice; the (16 MT) x 128-k activation tile of
+//     a unit is fetched once per workgroup (MT 16-byte loads per thread, a unit ahead), written to a double-buffered LDS image
+//     with chunk ^ (row & 15) swizzle and read as fragments by all four waves: one barrier per unit.
+// Weights never touch LDS: one raw_buffer_load (dwordx4) per lane and 32-k step, issued in one fixed order two units ahead
+// (2 x 4 KiB per wave in flight), waits counted by hipcc. GROUPED: one scale row per 128-k unit, applied to the unit's fp32
+// accumulators; channel-wise scales are applied once, in the epilogue. (GROUPED at MT = 4 holds 64 + 64 accumulators: it takes
+// more than the 256 registers of two workgroups per CU, so that one form is compiled for one.)
+template <typename scalar_t, int MT, int NW, bool GROUPED, bool STAGED>
+__global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_gemm_kernel(const W4Params p) {
+  static_assert(STAGED ? NW == 4 : MT == 1, "staged: 4 waves = 4 column groups; unstaged: one 16-row tile");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4, r = lane & 15;
+  const int N = p.N, K = p.K, M = p.M;
+  const int C = N / 64, total_units = K / 128;
+
+  // workgroup -> (column workgroup, K split). With 2 / 4 / 8 splits the XCD (= workgroup id % 8) selects the split: 8 / splits
+  // XCDs share one split's slice of the activations, each on its own column workgroups.
+  const int ncolwg = STAGED ? (C + 3) / 4 : C;
+  int colwg, split;
+  if (p.xcd_per > 0) {
+    const int lin = blockIdx.x;
+    split = (lin & 7) / p.xcd_per;
+    colwg = (lin >> 3) * p.xcd_per + (lin & 7) % p.xcd_per;
+  } else {
+    colwg = blockIdx.x;
+    split = blockIdx.y;
+  }
+  if (colwg >= ncolwg) return;  // padding workgroup (whole workgroup: no barrier is skipped)
+  const int cg = STAGED ? colwg * 4 + wave : colwg;
+  const bool col_ok = cg < C;
+  const int cl = min(cg, C - 1);  // column group used for the loads (a wave past N computes a valid group again, never stored)
+  const int m0 = blockIdx.z * (16 * MT);
+
+  // K slice in units of 128 k
+  constexpr int SLICES = STAGED ? 1 : NW;
+  const int workers = p.k_splits * SLICES;
+  const int per = (total_units + workers - 1) / workers;
+  const int worker = split * SLICES + (STAGED ? 0 : wave);
+  const int u0 = min(worker * per, total_units), u1 = min(u0 + per, total_units);
+
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(p.qw), 0, (K / 2) * N, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, M * K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.scales), 0, p.num_groups * N * 2, 0x00020000);
+  const int unit_bytes = C * 4096;  // one 128-k unit of all column groups
+  const int w_voff = cl * 4096 + lane * 16;
+  const int s_voff = (cl * 4 + g) * 32;
+  constexpr int kPast = 0x7ff00000;  // beyond every descriptor: the load returns zeros
+  // unstaged: the lane's own row; staged: chunk e = tid + 256 i of the tile image (row e >> 4, 16-byte chunk e & 15)
+  int a_voff[STAGED ? MT : 1], a_lds[STAGED ? MT : 1];
+  if constexpr (STAGED) {
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const int e = threadIdx.x + 256 * i, row = e >> 4, ch = e & 15;
+      a_voff[i] = (m0 + row < M) ? ((m0 + row) * K + 8 * ch) * 2 : kPast;
+      a_lds[i] = row * 256 + ((ch ^ (row & 15)) * 16);
+    }
+  } else {
+    a_voff[0] = (m0 + r < M) ? ((m0 + r) * K + 8 * g) * 2 : kPast;
+    a_lds[0] = 0;
+  }
+
+  constexpr int kTile = MT * 4096;  // staged activation image of one unit
+  __shared__ __attribute__((aligned(16))) char smem[STAGED ? 2 * kTile : NW * 4096];
+
+  struct Unit {
+    u32x4 q[4];
+    u32x4 a[STAGED ? 1 : 4];
+    u32x4 s[2];
+  };
+  // loads of one 32-k step / the scale row of unit u (past the slice: the last unit again, never consumed). sched_barrier pins
+  // the issue order: prologue and loop must queue the loads alike, or the merged wait counts at the loop head degrade.
+  auto load_step = [&](int u, int ks, Unit& U) {
+    u = min(u, total_units - 1);
+    U.q[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_voff, u * unit_bytes + ks * 1024, 2);  // aux 2: non-temporal
+    if constexpr (!STAGED) U.a[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_voff[0], (u * 128 + ks * 32) * 2, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto load_scales = [&](int u, Unit& U) {
+    if constexpr (GROUPED) {
+      u = min(u, total_units - 1);  // one group per unit
+      U.s[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, u * N * 2, 0);
+      U.s[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, u * N * 2, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto load_unit = [&](int u, Unit& U) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) load_step(u, ks, U);
+    load_scales(u, U);
+  };
+  u32x4 areg[STAGED ? MT : 1];
+  auto stage_load = [&](int u) {
+    if constexpr (STAGED) {
+      u = min(u, total_units - 1);
+#pragma unroll
+      for (int i = 0; i < MT; ++i) areg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_voff[i], u * 256, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto stage_store = [&](char* buf) {
+    if constexpr (STAGED) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i) *reinterpret_cast<u32x4*>(buf + a_lds[i]) = areg[i];
+    }
+  };
+
+  f32x4 acc[MT][4];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const uint32_t magic = 0x64006400u;
+
+  // consumes unit U (activations: its own registers, or the LDS image buf) and re-issues each register set for unit `next`
+  // as soon as it is free
+  auto compute_unit = [&](Unit& U, int next, const char* buf, bool reissue) {
+    f32x4 gacc[GROUPED ? MT : 1][4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      u32x4 bf[MT];
+      if constexpr (STAGED) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          bf[mt] = *reinterpret_cast<const u32x4*>(buf + (16 * mt + r) * 256 + (((4 * ks + g) ^ r) * 16));
+      } else {
+        bf[0] = U.a[ks];
+      }
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const u32x4 wf = w4_fragment<scalar_t>(U.q[ks][t], magic);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) {
+          if constexpr (GROUPED) gacc[mt][t] = mfma_w4<scalar_t>(wf, bf[mt], ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : gacc[mt][t]);
+          else acc[mt][t] = mfma_w4<scalar_t>(wf, bf[mt], acc[mt][t]);
+        }
+      }
+      if (reissue) load_step(next, ks, U);
+    }
+    if constexpr (GROUPED) {
+      union { u32x4 v[2]; scalar_t e[16]; } raw;
+      raw.v[0] = U.s[0];
+      raw.v[1] = U.s[1];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float sv = Scalar<scalar_t>::to_f32(raw.e[4 * t + j]);
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) acc[mt][t][j] = __builtin_fmaf(sv, gacc[mt][t][j], acc[mt][t][j]);
+        }
+      if (reissue) load_scales(next, U);
+    }
+  };
+
+  Unit ua, ub;
+  char* const buf0 = smem;
+  char* const buf1 = smem + (STAGED ? kTile : 0);
+  if (u0 < u1) {
+    stage_load(u0);
+    load_unit(u0, ua);
+    load_unit(u0 + 1, ub);
+    if constexpr (STAGED) {
+      stage_store(buf0);
+      stage_load(u0 + 1);
+      __syncthreads();
+    }
+    // whole pairs, then a peeled odd unit (its loads are already in ua; nothing is re-issued). Staged: a unit reads the image
+    // the previous iteration wrote before its barrier, and writes the other one, which every wave finished reading before that
+    // same barrier.
+    int u = u0;
+    for (; u + 1 < u1; u += 2) {
+      compute_unit(ua, u + 2, buf0, true);
+      if constexpr (STAGED) {
+        stage_store(buf1);
+        stage_load(u + 2);
+        __syncthreads();
+      }
+      compute_unit(ub, u + 3, buf1, true);
+      if constexpr (STAGED) {
+        stage_store(buf0);
+        stage_load(u + 3);
+        __syncthreads();
+      }
+    }
+    if (u < u1) compute_unit(ua, u, buf0, false);
+  }
+
+  // ---- epilogue ----
+  scalar_t* const cptr = reinterpret_cast<scalar_t*>(p.c);
+  if constexpr (STAGED) {
+    if (!col_ok) return;
+    union { u32x4 v[2]; scalar_t e[16]; } sc;
+    if constexpr (!GROUPED) {
+      sc.v[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, 0, 0);
+      sc.v[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, 0, 0);
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = m0 + 16 * mt + r;
+      if (m >= M) continue;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        f32x4 v = acc[mt][t];
+        if constexpr (!GROUPED) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] *= Scalar<scalar_t>::to_f32(sc.e[4 * t + j]);
+        }
+        const int64_t off = (int64_t)m * N + cg * 64 + 16 * t + 4 * g;
+        if (p.k_splits == 1) {
+          union { scalar_t h[4]; u32x2 u; } o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o.h[j] = Scalar<scalar_t>::from_f32(v[j]);
+          *reinterpret_cast<u32x2*>(cptr + off) = o.u;
+        } else {
+          *reinterpret_cast<f32x4*>(p.partial + (int64_t)split * M * N + off) = v;
+        }
+      }
+    }
+  } else {
+    // sum the NW K slices through LDS: thread e < 256 owns float4 e of the workgroup's [4 tiles][64 lanes] image
+    f32x4* red = reinterpret_cast<f32x4*>(smem);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) red[(wave * 4 + t) * 64 + lane] = acc[0][t];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 256; e += 64 * NW) {
+      f32x4 v = red[e];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) v += red[w * 256 + e];
+      const int t = e >> 6, el = e & 63, eg = el >> 4;
+      const int m = m0 + (el & 15);
+      if (m >= M) continue;
+      if constexpr (!GROUPED) {
+        union { u32x2 u; scalar_t e[4]; } sc;
+        sc.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const scalar_t*>(p.scales) + (cg * 4 + eg) * 16 + 4 * t);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] *= Scalar<scalar_t>::to_f32(sc.e[j]);
+      }
+      const int64_t off = (int64_t)m * N + cg * 64 + 16 * t + 4 * eg;
+      if (p.k_splits == 1) {
+        union { scalar_t h[4]; u32x2 u; } o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o.h[j] = Scalar<scalar_t>::from_f32(v[j]);
+        *reinterpret_cast<u32x2*>(cptr + off) = o.u;
+      } else {
+        *reinterpret_cast<f32x4*>(p.partial + (int64_t)split * M * N + off) = v;
+      }
+    }
+  }
+}
+
+// ---- dispatch --------------------------------------------------------------------------------------------------------
+// mt: 16-row tiles per workgroup (1: the unstaged form, 2 / 4: staged), nw: waves of the unstaged form (4 / 8), splits: K splits
+// across workgroups - only to fill the 256 CUs, and only while every wave keeps >= 2 units. NMX_W4A16 = "mt,nw,splits" forces
+// any of them for sweeps and tests (0 = keep the default).
+W4Cfg w4_pick(int M, int N, int K) {
+  W4Cfg c;
+  // Measured (tools/lean_sweep.py N: family, Llama-3-8B shapes): the unstaged form wins at M = 1 everywhere and
+  // at M = 16 on qkv / o; at M = 16 the big matrices (down, gate_up: >= 24 MiB of weights) take the staged 32-row tile
+  // (16.9 vs 19.3 us, 9.9 vs 10.7), and at M = 64 the small ones (qkv, o) take two 32-row blocks (10.9 vs 11.6, 7.9 vs 9.7).
+  const bool big = (int64_t)K * N / 2 >= (24ll << 20);
+  c.mt = M <= 8 ? 1 : (M <= 16 ? (big ? 2 : 1) : (M <= 32 ? 2 : (M <= 64 && !big ? 2 : 4)));
+  c.nw = 4;
+  c.splits = 1;
+  int f_mt = 0, f_nw = 0, f_splits = 0;
+  if (const char* e = nmx_tune(NMX_TUNE_W4A16)) sscanf(e, "%d,%d,%d", &f_mt, &f_nw, &f_splits);
+  if (f_mt == 1 || f_mt == 2 || f_mt == 4) c.mt = f_mt;
+  if (c.mt == 1 && f_nw == 8) c.nw = 8;
+  const int units = K / 128, groups = N / 64;
+  const int row_blocks = ceil_div(M, 16 * c.mt);
+  const int wgs = (c.mt == 1 ? groups : ceil_div(groups, 4)) * row_blocks;
+  const int slices = c.mt == 1 ? c.nw : 1;
+  while (wgs * c.splits * 2 <= 256 && units / (slices * c.splits * 2) >= 2 && c.splits < 16) c.splits *= 2;
+  if (f_splits >= 1) c.splits = f_splits;
+  c.splits = std::max(1, std::min(std::min(c.splits, units), 64));
+  return c;
+}
+
+template <typename scalar_t, bool GROUPED>
+int w4_launch(const W4Params& p, const W4Cfg& cfg, hipStream_t stream) {
+  const int C = p.N / 64;
+  const int ncolwg = cfg.mt == 1 ? C : ceil_div(C, 4);
+  dim3 grid(ncolwg, p.k_splits, ceil_div(p.M, 16 * cfg.mt));
+  if (p.xcd_per > 0) grid = dim3(ceil_div(ncolwg, p.xcd_per) * 8, 1, grid.z);
+  if (cfg.mt == 1 && cfg.nw == 8) w4a16_gemm_kernel<scalar_t, 1, 8, GROUPED, false><<<grid, 512, 0, stream>>>(p);
+  else if (cfg.mt == 1) w4a16_gemm_kernel<scalar_t, 1, 4, GROUPED, false><<<grid, 256, 0, stream>>>(p);
+  else if (cfg.mt == 2) w4a16_gemm_kernel<scalar_t, 2, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
+  else w4a16_gemm_kernel<scalar_t, 4, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
+  NMX_LAUNCH_CHECK();
+  return NMX_OK;
+}
+
+int w4_common(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+              int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int defer,
+              int* splits_out, hipStream_t stream) {
+  if (splits_out != nullptr) *splits_out = 1;
+  NMX_CHECK(dtype == NMX_F16 || dtype == NMX_BF16, NMX_ERR_UNSUPPORTED, "w4a16_gemm only supports bfloat16 and float16");
+  NMX_CHECK(size_m >= 0 && size_n > 0 && size_k > 0, NMX_ERR_INVALID_ARG, "w4a16_gemm: size_m = %d, size_n = %d, size_k = %d", size_m,
+            size_n, size_k);
+  NMX_CHECK(nmx_w4a16_supported(size_n, size_k, num_groups, 4, 0), NMX_ERR_UNSUPPORTED,
+            "w4a16_gemm: size_k = %d must be a multiple of 128, size_n = %d of 64, num_groups = %d one or size_k / 128", size_k, size_n,
+            num_groups);
+  NMX_CHECK((int64_t)size_m * size_k * 2 <= 0x7ff00000ll && (int64_t)size_k * size_n < (1ll << 32) && (int64_t)size_m * size_n < (1ll << 31),
+            NMX_ERR_UNSUPPORTED, "w4a16_gemm: operand beyond the 2 GiB a buffer descriptor addresses");
+  NMX_CHECK(a != nullptr && qweight_native != nullptr && scales_native != nullptr && c != nullptr, NMX_ERR_INVALID_ARG,
+            "w4a16_gemm: null operand");
+  NMX_CHECK(((uintptr_t)a % 16 == 0) && ((uintptr_t)qweight_native % 16 == 0) && ((uintptr_t)scales_native % 16 == 0) &&
+                ((uintptr_t)c % 8 == 0) && ((uintptr_t)scratch % 16 == 0),
+            NMX_ERR_INVALID_ARG, "w4a16_gemm: operands must be 16-byte aligned");
+  if (size_m == 0) return NMX_OK;
+  W4Cfg cfg = w4_pick(size_m, size_n, size_k);
+  const int64_t slab = (int64_t)size_m * size_n * sizeof(float);
+  if (scratch == nullptr) scratch_bytes = 0;
+  if ((int64_t)cfg.splits * slab > scratch_bytes) cfg.splits = (int)std::max<int64_t>(1, scratch_bytes / slab);  // fewer splits, never past the scratch
+  W4Params p;
+  p.a = a; p.qw = qweight_native; p.scales = scales_native; p.c = c; p.partial = reinterpret_cast<float*>(scratch);
+  p.M = size_m; p.N = size_n; p.K = size_k; p.num_groups = num_groups; p.k_splits = cfg.splits;
+  const char* xs = nmx_tune(NMX_TUNE_GEMM_XCD_SPLIT);
+  const bool xcd = (xs == nullptr || atoi(xs) != 0) && (cfg.splits == 2 || cfg.splits == 4 || cfg.splits == 8);
+  p.xcd_per = xcd ? 8 / cfg.splits : 0;
+  int rc;
+  if (dtype == NMX_F16) rc = num_groups > 1 ? w4_launch<f16, true>(p, cfg, stream) : w4_launch<f16, false>(p, cfg, stream);
+  else rc = num_groups > 1 ? w4_launch<bf16, true>(p, cfg, stream) : w4_launch<bf16, false>(p, cfg, stream);
+  if (rc != NMX_OK || cfg.splits == 1) return rc;
+  if (defer) {
+    *splits_out = cfg.splits;
+    return NMX_OK;
+  }
+  return nmx_splitk_reduce(c, p.partial, cfg.splits, size_m, size_n, dtype, stream);
+}
+
+}  // namespace
+
+extern "C" int nmx_w4a16_supported(int size_n, int size_k, int num_groups, int num_bits, int has_act_order) {
+  return num_bits == 4 && !has_act_order && size_n > 0 && size_k > 0 && size_k % 128 == 0 && size_n % 64 == 0 &&
+                 (num_groups == 1 || num_groups == size_k / 128)
+             ? 1 : 0;
+}
+
+extern "C" int nmx_w4a16_repack(const int32_t* qweight, const void* scales, int32_t* qweight_native, void* scales_native,
+                                int size_k, int size_n, int num_groups, int dtype, nmx_stream_t stream) {
+  NMX_CHECK(dtype == NMX_F16 || dtype == NMX_BF16, NMX_ERR_UNSUPPORTED, "w4a16_repack only supports bfloat16 and float16 scales");
+  NMX_CHECK(nmx_w4a16_supported(size_n, size_k, num_groups, 4, 0), NMX_ERR_UNSUPPORTED,
+            "w4a16_repack: size_k = %d must be a multiple of 128, size_n = %d of 64, num_groups = %d one or size_k / 128", size_k, size_n,
+            num_groups);
+  NMX_CHECK(qweight != nullptr && scales != nullptr && qweight_native != nullptr && scales_native != nullptr &&
+                qweight != qweight_native && scales != scales_native,
+            NMX_ERR_INVALID_ARG, "w4a16_repack: null or aliased operand");
+  const int64_t words = (int64_t)(size_k / 8) * size_n;
+  w4a16_repack_kernel<<<(unsigned)ceil_div64(words, 256), 256, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const uint32_t*>(qweight), reinterpret_cast<const uint16_t*>(scales), reinterpret_cast<uint32_t*>(qweight_native),
+      reinterpret_cast<uint16_t*>(scales_native), size_k, size_n, num_groups);
+  NMX_LAUNCH_CHECK();
+  return NMX_OK;
+}
+
+extern "C" int64_t nmx_w4a16_gemm_scratch_bytes(int size_m, int size_n, int size_k) {
+  if (size_m <= 0 || size_n <= 0 || size_k < 128) return 0;
+  const int splits = w4_pick(size_m, size_n, size_k).splits;
+  return splits > 1 ? (int64_t)splits * size_m * size_n * sizeof(float) : 0;
+}
+
+extern "C" int nmx_w4a16_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                              int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
+                              nmx_stream_t stream) {
+  return w4_common(a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 0, nullptr,
+                   (hipStream_t)stream);
+}
+
+extern "C" int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                                       int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
+                                       int* splits_out, nmx_stream_t stream) {
+  NMX_CHECK(splits_out != nullptr, NMX_ERR_INVALID_ARG, "splits_out is null");
+  return w4_common(a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 1, splits_out,
+                   (hipStream_t)stream);
+}

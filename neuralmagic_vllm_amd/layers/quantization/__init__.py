@@ -8,6 +8,7 @@ from neuralmagic_vllm_amd.layers.quantization.fp8 import Fp8Config
 from neuralmagic_vllm_amd.layers.quantization.gptq import GPTQConfig
 from neuralmagic_vllm_amd.layers.quantization.gptq_marlin import GPTQMarlinConfig
 from neuralmagic_vllm_amd.layers.quantization.gptq_marlin_24 import GPTQMarlin24Config
+from neuralmagic_vllm_amd.layers.quantization.gptq_native import GPTQNativeConfig
 from neuralmagic_vllm_amd.layers.quantization.marlin import MarlinConfig
 
 QUANTIZATION_METHODS: Dict[str, Type[QuantizationConfig]] = {
@@ -18,6 +19,7 @@ QUANTIZATION_METHODS: Dict[str, Type[QuantizationConfig]] = {
     "gptq": GPTQConfig,
     "gptq_marlin": GPTQMarlinConfig,  # must stay before plain gptq in override order (reference comment, __init__.py:32-36)
     "marlin": MarlinConfig,
+    "gptq_native": GPTQNativeConfig,  # opt-in (CDNA4-native W4A16 layout): last, its override only answers to its own name
 }
 
 

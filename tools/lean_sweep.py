@@ -4,7 +4,8 @@ configuration against the default path of the skinny kernel on the same inputs.
 
 usage (GPU box): python3 tools/lean_sweep.py [M ...] > gpurun_out/lean_sweep.txt
 cfg strings: "D:auto" = default dispatch, "L:nw,splits[,mt[,ws]]" = marlin_decode_kernel, "G:ngrp" = marlin_large_kernel, "S:mt,ng,splits[,w8]" = marlin_gemm_kernel, "S:auto" its heuristic,
-"X:splits" = marlin_dma_kernel."""
+"X:splits" = marlin_dma_kernel, "N:auto" / "N:mt,nw,splits" = w4a16_gemm on the CDNA4-native layout (NMX_W4A16; 0 = default), checked
+against its own default dispatch (the same random words mean other weights there than in Marlin's order)."""
 import os
 import sys
 
@@ -24,9 +25,13 @@ dev = "cuda:0"
 
 def set_cfg(cfg):
     from neuralmagic_vllm_amd import _lib
-    for k in ("NMX_GEMM_CFG", "NMX_GEMM_LEAN", "NMX_GEMM_LARGE", "NMX_GEMM_LARGE_NGRP", "NMX_GEMM_WIDE", "NMX_GEMM_DMA"):
+    for k in ("NMX_GEMM_CFG", "NMX_GEMM_LEAN", "NMX_GEMM_LARGE", "NMX_GEMM_LARGE_NGRP", "NMX_GEMM_WIDE", "NMX_GEMM_DMA", "NMX_W4A16"):
         _lib.set_tuning(k, None)
     kind, val = cfg.split(":")
+    if kind == "N":  # w4a16_gemm_kernel "mt,nw,splits"
+        if val != "auto":
+            _lib.set_tuning("NMX_W4A16", val)
+        return
     if kind == "D":  # default dispatch, no override
         return
     if kind == "X":  # marlin_dma_kernel with val K splits
@@ -121,6 +126,25 @@ def main():
                     us = time_graph(run_t) / NL
                     print(f"{'hipBLASLt-fp16':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {(2 * K * N + 2 * M * K + 2 * M * N) / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  (dense fp16 yardstick)", flush=True)
                     del dws
+                    continue
+                if cfg.startswith("N:"):  # the native layout: the same 32 word tensors, viewed [K / 128, 16 N]
+                    try:
+                        wn = [(w[0].view(K // 128, N * 16), w[1]) for w in ws]
+                        set_cfg("N:auto")
+                        nref = ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K).float()
+                        set_cfg(cfg)
+                        err = ((ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K).float() - nref).abs().mean() / nref.abs().mean()).item()
+                        gemm = ops.w4a16_gemm_deferred if os.environ.get("LEAN_SWEEP_DEFER") == "1" else ops.w4a16_gemm
+
+                        def run_n():
+                            for w in wn:
+                                gemm(x, w[0], w[1], M, N, K)
+
+                        us = time_graph(run_n) / NL
+                        print(f"{'w4a16-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_native_default={err:.2e}", flush=True)
+                    except Exception as ex:  # noqa: BLE001
+                        print(f"{name:8} M={M:3d} {cfg:12} FAILED {ex}", flush=True)
+                        torch.cuda.synchronize()
                     continue
                 set_cfg(cfg)
                 try:
