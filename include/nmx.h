@@ -333,11 +333,15 @@ int nmx_awq_marlin_gemm_deferred(const void* a, const int32_t* q, const void* sc
  * nmx_w4a16_gemm_scratch_bytes: bytes of fp32 split-K slabs the dispatch can use (0: no split). The GEMM uses fewer splits with less.
  * nmx_w4a16_gemm_deferred: as nmx_gptq_marlin_gemm_deferred - with *splits_out > 1 the fp32 slabs [*splits_out, size_m, size_n]
  * are left at the start of scratch for nmx_splitk_reduce or a *_splitk consumer and c is untouched. size_m is free (row blocks
- * of 64 above 64 rows). All entries only enqueue. */
+ * of 64 above 64 rows; NMX_W4A16 = "8,0,0" forces w4a16_tall_kernel: 128 rows per workgroup, every weight fragment converted
+ * once per workgroup). nmx_w4a16_gemm_plan: what the GEMM launches for a shape under the current NMX_W4A16 override - *mt 16-row
+ * tiles per workgroup (1 / 2 / 4, 8 = tall), *nw waves of the mt = 1 form (4 otherwise), *splits K splits -
+ * nmx_w4a16_gemm_scratch_bytes is *splits slabs of it. All entries only enqueue. */
 int nmx_w4a16_supported(int size_n, int size_k, int num_groups, int num_bits, int has_act_order);
 int nmx_w4a16_repack(const int32_t* qweight, const void* scales, int32_t* qweight_native, void* scales_native, int size_k,
                      int size_n, int num_groups, int dtype, nmx_stream_t stream);
 int64_t nmx_w4a16_gemm_scratch_bytes(int size_m, int size_n, int size_k);
+int nmx_w4a16_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits);
 int nmx_w4a16_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
                    int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, nmx_stream_t stream);
 int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,

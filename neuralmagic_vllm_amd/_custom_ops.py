@@ -1088,6 +1088,15 @@ def w4a16_gemm(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: tor
     return _w4a16_call("nmx_w4a16_gemm", a, qweight_native, scales_native, size_m, size_n, size_k)[0]
 
 
+def w4a16_gemm_plan(size_m: int, size_n: int, size_k: int):
+    """(mt, nw, splits) that w4a16_gemm launches for this shape under the current NMX_W4A16 override: mt 16-row tiles per
+    workgroup (8 = the tall kernel), nw waves of the mt = 1 form (4 otherwise), splits K splits across workgroups."""
+    mt, nw, splits = c_int(0), c_int(0), c_int(0)
+    _lib.check(_lib.lib().nmx_w4a16_gemm_plan(c_int(size_m), c_int(size_n), c_int(size_k), ctypes.byref(mt), ctypes.byref(nw),
+                                              ctypes.byref(splits)))
+    return mt.value, nw.value, splits.value
+
+
 def w4a16_gemm_deferred(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor, size_m: int, size_n: int,
                         size_k: int) -> DeferredGemm:
     """w4a16_gemm whose split-K partial sums are left for the consumer op, like gptq_marlin_gemm_deferred."""

@@ -30,6 +30,7 @@ def lib() -> ctypes.CDLL:
                    "nmx_w4a16_gemm_scratch_bytes"):
             getattr(_lib, fn).restype = ctypes.c_int64
         _lib.nmx_tuning_set.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
+        _lib.nmx_w4a16_gemm_plan.argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3
     return _lib
 
 

@@ -357,10 +357,199 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_g
   }
 }
 
+// ---- the tall GEMM (MT = 8): 128 rows per workgroup, every weight fragment converted ONCE per workgroup and used against 8
+// B fragments. 4 waves on 4 adjacent column groups share one K slice, as the staged form above; a wave owns
+// one 64-column group x 128 rows = 32 f32x4 accumulators (128 registers; GROUPED doubles them for the unit's sums: one wave per
+// SIMD, one workgroup per CU). The 128-row x 128-k activation image of a unit (32 KiB) is fetched once per workgroup a unit
+// ahead (8 x 16-byte loads per thread), double-buffered in LDS with the same swizzle, one barrier per unit.
+// Weight stream: a ring of 8 dwordx4 registers per lane = the wave's steps of the next 2 units, each slot re-issued two units
+// ahead right after its step; the loop body is 2 units so that every slot is a fixed register and the LDS image is j & 1. A
+// slice of any length (0, 1, odd) leaves the loop after its last unit; loads past the slice read the last unit again and are
+// never consumed. GROUPED: one scale row in flight, a unit ahead. No scratch, except bf16 GROUPED (about 200 bytes per lane with
+// 256 accumulators; a one-unit ring and one or two fragments per pass did not remove it).
+template <typename scalar_t, bool GROUPED>
+__global__ __launch_bounds__(256, 1) void w4a16_tall_kernel(const W4Params p) {
+  constexpr int RT = 8;  // 16-row tiles
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4, r = lane & 15;
+  const int N = p.N, K = p.K, M = p.M;
+  const int C = N / 64, total_units = K / 128;
+
+  const int ncolwg = (C + 3) / 4;
+  int colwg, split;
+  if (p.xcd_per > 0) {  // as w4a16_gemm_kernel: the XCD selects the K split
+    const int lin = blockIdx.x;
+    split = (lin & 7) / p.xcd_per;
+    colwg = (lin >> 3) * p.xcd_per + (lin & 7) % p.xcd_per;
+  } else {
+    colwg = blockIdx.x;
+    split = blockIdx.y;
+  }
+  if (colwg >= ncolwg) return;  // padding workgroup (whole workgroup: no barrier is skipped)
+  const int cg = colwg * 4 + wave;
+  const bool col_ok = cg < C;
+  const int cl = min(cg, C - 1);
+  const int m0 = blockIdx.z * (16 * RT);
+  const int per = (total_units + p.k_splits - 1) / p.k_splits;
+  const int u0 = min(split * per, total_units), u1 = min(u0 + per, total_units);  // may be empty: the slab gets zeros
+
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(p.qw), 0, (K / 2) * N, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, M * K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.scales), 0, p.num_groups * N * 2, 0x00020000);
+  const int unit_bytes = C * 4096;
+  const int w_voff = cl * 4096 + lane * 16;
+  const int s_voff = (cl * 4 + g) * 32;
+  constexpr int kPast = 0x7ff00000;
+  // chunk e = tid + 256 i of the tile image: row e >> 4 = 16 i + (tid >> 4), 16-byte chunk tid & 15
+  int a_voff[RT];
+  const int a_row = threadIdx.x >> 4, a_ch = threadIdx.x & 15;
+  const int a_lds = a_row * 256 + ((a_ch ^ a_row) * 16);  // + 4096 i
+#pragma unroll
+  for (int i = 0; i < RT; ++i) {
+    const int row = m0 + 16 * i + a_row;
+    a_voff[i] = row < M ? (row * K + 8 * a_ch) * 2 : kPast;
+  }
+  int b_lds[4];  // the lane's B fragment of step ks, row tile 0 (+ 4096 mt)
+#pragma unroll
+  for (int ks = 0; ks < 4; ++ks) b_lds[ks] = r * 256 + (((4 * ks + g) ^ r) * 16);
+
+  constexpr int kTile = RT * 4096;
+  __shared__ __attribute__((aligned(16))) char smem[2 * kTile];
+
+  u32x4 q[8], sc[2], areg[RT];
+  auto load_step = [&](int u, int slot) {  // slot = 4 * (unit & 1) + step
+    u = min(u, total_units - 1);
+    q[slot] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_voff, u * unit_bytes + (slot & 3) * 1024, 2);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto load_scales = [&](int u) {
+    if constexpr (GROUPED) {
+      u = min(u, total_units - 1);
+      sc[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, u * N * 2, 0);
+      sc[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, u * N * 2, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto stage_load = [&](int u) {
+    u = min(u, total_units - 1);
+#pragma unroll
+    for (int i = 0; i < RT; ++i) areg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_voff[i], u * 256, 0);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto stage_store = [&](char* buf) {
+#pragma unroll
+    for (int i = 0; i < RT; ++i) *reinterpret_cast<u32x4*>(buf + a_lds + 4096 * i) = areg[i];
+  };
+
+  f32x4 acc[RT][4];
+#pragma unroll
+  for (int mt = 0; mt < RT; ++mt)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const uint32_t magic = 0x64006400u;
+
+  // unit u = unit j of the trip: its steps from ring slots 4 j .., activations from image buf
+  auto compute_unit = [&](int u, int j, const char* buf) {
+    f32x4 gacc[GROUPED ? RT : 1][4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      // the step's four fragments first, then the row tiles one LDS read ahead of their MFMAs: few registers live
+      u32x4 wf[4];
+#pragma unroll
+      for (int t = 0; t < 4; ++t) wf[t] = w4_fragment<scalar_t>(q[4 * j + ks][t], magic);
+      u32x4 b0 = *reinterpret_cast<const u32x4*>(buf + b_lds[ks]);
+#pragma unroll
+      for (int mt = 0; mt < RT; ++mt) {
+        const u32x4 b1 = *reinterpret_cast<const u32x4*>(buf + b_lds[ks] + 4096 * (mt + 1 < RT ? mt + 1 : mt));
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+          if constexpr (GROUPED) gacc[mt][t] = mfma_w4<scalar_t>(wf[t], b0, ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : gacc[mt][t]);
+          else acc[mt][t] = mfma_w4<scalar_t>(wf[t], b0, acc[mt][t]);
+        }
+        b0 = b1;
+        if constexpr (GROUPED) __builtin_amdgcn_sched_barrier(0);  // keeps the reads from being hoisted: 256 accumulators
+      }
+      load_step(u + 2, 4 * j + ks);
+    }
+    if constexpr (GROUPED) {
+      union { u32x4 v[2]; scalar_t e[16]; } raw;
+      raw.v[0] = sc[0];
+      raw.v[1] = sc[1];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int jj = 0; jj < 4; ++jj) {
+          const float sv = Scalar<scalar_t>::to_f32(raw.e[4 * t + jj]);
+#pragma unroll
+          for (int mt = 0; mt < RT; ++mt) acc[mt][t][jj] = __builtin_fmaf(sv, gacc[mt][t][jj], acc[mt][t][jj]);
+        }
+      load_scales(u + 1);
+    }
+  };
+
+  char* const buf0 = smem;
+  char* const buf1 = smem + kTile;
+  if (u0 < u1) {
+    stage_load(u0);
+#pragma unroll
+    for (int slot = 0; slot < 8; ++slot) load_step(u0 + (slot >> 2), slot);  // the order in which the loop re-issues them
+    load_scales(u0);
+    stage_store(buf0);
+    stage_load(u0 + 1);
+    __syncthreads();
+    // Unit j of a trip reads image j, written before the previous barrier, and writes the other one, which every wave
+    // finished reading before that same barrier.
+    [&] {
+      for (int u = u0;; u += 2) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          compute_unit(u + j, j, j ? buf1 : buf0);
+          stage_store(j ? buf0 : buf1);
+          stage_load(u + j + 2);
+          __syncthreads();
+          if (u + j + 1 >= u1) return;
+        }
+      }
+    }();
+  }
+
+  // ---- epilogue: scale (channel-wise), store ----
+  if (!col_ok) return;
+  scalar_t* const cptr = reinterpret_cast<scalar_t*>(p.c);
+  union { u32x4 v[2]; scalar_t e[16]; } cs;
+  if constexpr (!GROUPED) {
+    cs.v[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, 0, 0);
+    cs.v[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, 0, 0);
+  }
+#pragma unroll
+  for (int mt = 0; mt < RT; ++mt) {
+    const int m = m0 + 16 * mt + r;
+    if (m >= M) continue;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      f32x4 v = acc[mt][t];
+      if constexpr (!GROUPED) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] *= Scalar<scalar_t>::to_f32(cs.e[4 * t + j]);
+      }
+      const int64_t off = (int64_t)m * N + cg * 64 + 16 * t + 4 * g;
+      if (p.k_splits == 1) {
+        union { scalar_t h[4]; u32x2 u; } o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o.h[j] = Scalar<scalar_t>::from_f32(v[j]);
+        *reinterpret_cast<u32x2*>(cptr + off) = o.u;
+      } else {
+        *reinterpret_cast<f32x4*>(p.partial + (int64_t)split * M * N + off) = v;
+      }
+    }
+  }
+}
+
 // ---- dispatch --------------------------------------------------------------------------------------------------------
-// mt: 16-row tiles per workgroup (1: the unstaged form, 2 / 4: staged), nw: waves of the unstaged form (4 / 8), splits: K splits
-// across workgroups - only to fill the 256 CUs, and only while every wave keeps >= 2 units. NMX_W4A16 = "mt,nw,splits" forces
-// any of them for sweeps and tests (0 = keep the default).
+// mt: 16-row tiles per workgroup (1: the unstaged form, 2 / 4: staged, 8: the tall kernel), nw: waves of the unstaged form
+// (4 / 8), splits: K splits across workgroups - only to fill the 256 CUs, and only while every wave keeps >= 2 units (the tall
+// kernel: >= 4). NMX_W4A16 = "mt,nw,splits" forces any of them for sweeps and tests (0 = keep the default).
 W4Cfg w4_pick(int M, int N, int K) {
   W4Cfg c;
   // Measured (tools/lean_sweep.py N: family, Llama-3-8B shapes): the unstaged form wins at M = 1 everywhere and
@@ -368,17 +557,21 @@ W4Cfg w4_pick(int M, int N, int K) {
   // (16.9 vs 19.3 us, 9.9 vs 10.7), and at M = 64 the small ones (qkv, o) take two 32-row blocks (10.9 vs 11.6, 7.9 vs 9.7).
   const bool big = (int64_t)K * N / 2 >= (24ll << 20);
   c.mt = M <= 8 ? 1 : (M <= 16 ? (big ? 2 : 1) : (M <= 32 ? 2 : (M <= 64 && !big ? 2 : 4)));
+  // The tall kernel (mt = 8) is never the default: at one workgroup per CU it beat MT = 4 on one measured point only (gate_up
+  // at M = 256, fp16 group 128, 82.2 vs 85.1 us) and loses by 1.1 - 1.7x on every other shape at M = 128 / 256
+  // (profiles/w4a16_tall_ab.txt); bf16 and channel-wise were not measured and its bf16 GROUPED form spills.
   c.nw = 4;
   c.splits = 1;
   int f_mt = 0, f_nw = 0, f_splits = 0;
   if (const char* e = nmx_tune(NMX_TUNE_W4A16)) sscanf(e, "%d,%d,%d", &f_mt, &f_nw, &f_splits);
-  if (f_mt == 1 || f_mt == 2 || f_mt == 4) c.mt = f_mt;
+  if (f_mt == 1 || f_mt == 2 || f_mt == 4 || f_mt == 8) c.mt = f_mt;
   if (c.mt == 1 && f_nw == 8) c.nw = 8;
   const int units = K / 128, groups = N / 64;
   const int row_blocks = ceil_div(M, 16 * c.mt);
   const int wgs = (c.mt == 1 ? groups : ceil_div(groups, 4)) * row_blocks;
   const int slices = c.mt == 1 ? c.nw : 1;
-  while (wgs * c.splits * 2 <= 256 && units / (slices * c.splits * 2) >= 2 && c.splits < 16) c.splits *= 2;
+  const int min_units = c.mt == 8 ? 4 : 2;
+  while (wgs * c.splits * 2 <= 256 && units / (slices * c.splits * 2) >= min_units && c.splits < 16) c.splits *= 2;
   if (f_splits >= 1) c.splits = f_splits;
   c.splits = std::max(1, std::min(std::min(c.splits, units), 64));
   return c;
@@ -390,7 +583,8 @@ int w4_launch(const W4Params& p, const W4Cfg& cfg, hipStream_t stream) {
   const int ncolwg = cfg.mt == 1 ? C : ceil_div(C, 4);
   dim3 grid(ncolwg, p.k_splits, ceil_div(p.M, 16 * cfg.mt));
   if (p.xcd_per > 0) grid = dim3(ceil_div(ncolwg, p.xcd_per) * 8, 1, grid.z);
-  if (cfg.mt == 1 && cfg.nw == 8) w4a16_gemm_kernel<scalar_t, 1, 8, GROUPED, false><<<grid, 512, 0, stream>>>(p);
+  if (cfg.mt == 8) w4a16_tall_kernel<scalar_t, GROUPED><<<grid, 256, 0, stream>>>(p);
+  else if (cfg.mt == 1 && cfg.nw == 8) w4a16_gemm_kernel<scalar_t, 1, 8, GROUPED, false><<<grid, 512, 0, stream>>>(p);
   else if (cfg.mt == 1) w4a16_gemm_kernel<scalar_t, 1, 4, GROUPED, false><<<grid, 256, 0, stream>>>(p);
   else if (cfg.mt == 2) w4a16_gemm_kernel<scalar_t, 2, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
   else w4a16_gemm_kernel<scalar_t, 4, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
@@ -459,6 +653,17 @@ extern "C" int nmx_w4a16_repack(const int32_t* qweight, const void* scales, int3
       reinterpret_cast<const uint32_t*>(qweight), reinterpret_cast<const uint16_t*>(scales), reinterpret_cast<uint32_t*>(qweight_native),
       reinterpret_cast<uint16_t*>(scales_native), size_k, size_n, num_groups);
   NMX_LAUNCH_CHECK();
+  return NMX_OK;
+}
+
+extern "C" int nmx_w4a16_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits) {
+  NMX_CHECK(mt != nullptr && nw != nullptr && splits != nullptr, NMX_ERR_INVALID_ARG, "w4a16_gemm_plan: null output");
+  NMX_CHECK(size_m > 0 && size_n > 0 && size_k >= 128, NMX_ERR_INVALID_ARG, "w4a16_gemm_plan: size_m = %d, size_n = %d, size_k = %d", size_m,
+            size_n, size_k);
+  const W4Cfg c = w4_pick(size_m, size_n, size_k);
+  *mt = c.mt;
+  *nw = c.nw;
+  *splits = c.splits;
   return NMX_OK;
 }
 

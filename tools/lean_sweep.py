@@ -4,8 +4,9 @@ configuration against the default path of the skinny kernel on the same inputs.
 
 usage (GPU box): python3 tools/lean_sweep.py [M ...] > gpurun_out/lean_sweep.txt
 cfg strings: "D:auto" = default dispatch, "L:nw,splits[,mt[,ws]]" = marlin_decode_kernel, "G:ngrp" = marlin_large_kernel, "S:mt,ng,splits[,w8]" = marlin_gemm_kernel, "S:auto" its heuristic,
-"X:splits" = marlin_dma_kernel, "N:auto" / "N:mt,nw,splits" = w4a16_gemm on the CDNA4-native layout (NMX_W4A16; 0 = default), checked
-against its own default dispatch (the same random words mean other weights there than in Marlin's order)."""
+"X:splits" = marlin_dma_kernel, "N:auto" / "N:mt,nw,splits" = w4a16_gemm on the CDNA4-native layout (NMX_W4A16; 0 = default; mt 1 / 2 / 4
+= w4a16_gemm_kernel, 8 = w4a16_tall_kernel), checked against the 64-row form "4,0,1" (the
+same random words mean other weights there than in Marlin's order); the line ends with the plan launched and its fp32 slab bytes."""
 import os
 import sys
 
@@ -130,9 +131,11 @@ def main():
                 if cfg.startswith("N:"):  # the native layout: the same 32 word tensors, viewed [K / 128, 16 N]
                     try:
                         wn = [(w[0].view(K // 128, N * 16), w[1]) for w in ws]
-                        set_cfg("N:auto")
+                        set_cfg("N:4,0,1")
                         nref = ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K).float()
                         set_cfg(cfg)
+                        mt, nw, splits = ops.w4a16_gemm_plan(M, N, K)
+                        slab = splits * M * N * 4 if splits > 1 else 0
                         err = ((ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K).float() - nref).abs().mean() / nref.abs().mean()).item()
                         gemm = ops.w4a16_gemm_deferred if os.environ.get("LEAN_SWEEP_DEFER") == "1" else ops.w4a16_gemm
 
@@ -141,7 +144,7 @@ def main():
                                 gemm(x, w[0], w[1], M, N, K)
 
                         us = time_graph(run_n) / NL
-                        print(f"{'w4a16-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_native_default={err:.2e}", flush=True)
+                        print(f"{'w4a16-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_native_mt4={err:.2e}  plan={mt},{nw},{splits} slab={slab}", flush=True)
                     except Exception as ex:  # noqa: BLE001
                         print(f"{name:8} M={M:3d} {cfg:12} FAILED {ex}", flush=True)
                         torch.cuda.synchronize()
