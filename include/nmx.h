@@ -348,6 +348,28 @@ int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_native, const 
                             int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int* splits_out,
                             nmx_stream_t stream);
 
+/* The 8-bit form of the native layout (nmx_w4a16_supported(.., num_bits = 8, ..): the shape rules of 4 bits). Checkpoint qweight
+ * [size_k / 4, size_n] int32, code k % 4 of row k / 4 at bits 8 (k % 4); W[k, n] = (q - 128) * s[group(k), n]. The contract:
+ *   qweight_native  int32 [size_k / 128, size_n * 32], element order [u = k / 128][c = n / 64][s][h][lane l = 16 g + r][w]:
+ *     word (u, c, s, h, l, w) holds the 4 codes of column n = 64 c + 16 t + r, tile t = 2 h + (w >> 1), at
+ *     k = 128 u + 32 s + 8 g + 4 (w & 1) + i, i = 0 .. 3, code i in byte i - it is checkpoint word
+ *     (32 u + 8 s + 2 g + (w & 1), n) unchanged: bytes in k order need no shift (v_perm_b32 / v_cvt_f32_ubyteN select them). A
+ *     lane's 16-byte load = the complete A fragments (two words each) of two tiles for one 32-k step; two loads per lane and
+ *     step, a wave reads 8 KiB contiguous per 128-k unit. size_k * size_n / 4 words.
+ *   scales_native   as for 4 bits.
+ * q - 128 is converted exactly (never folded into a sum(a) term), products are summed in fp32 per 128-k group and the group's sum
+ * is multiplied by s in fp32. The entries mirror nmx_w4a16_*; they read the same NMX_W4A16 override. There is no 128-row form:
+ * a forced mt = 8 runs, and nmx_w8a16_gemm_plan reports, mt = 4. */
+int nmx_w8a16_repack(const int32_t* qweight, const void* scales, int32_t* qweight_native, void* scales_native, int size_k,
+                     int size_n, int num_groups, int dtype, nmx_stream_t stream);
+int64_t nmx_w8a16_gemm_scratch_bytes(int size_m, int size_n, int size_k);
+int nmx_w8a16_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits);
+int nmx_w8a16_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                   int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, nmx_stream_t stream);
+int nmx_w8a16_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                            int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int* splits_out,
+                            nmx_stream_t stream);
+
 /* marlin_gemm (csrc/quantization/marlin/dense/marlin_cuda_kernel.cu:1045-1136): int4, fp16, groups of 128 or
  * channel-wise, weights Marlin-packed in the checkpoint. */
 int nmx_marlin_gemm(const void* a, const int32_t* b_q_weight, const void* b_scales, void* c,

@@ -1043,65 +1043,75 @@ def awq_marlin_gemm_deferred(a: torch.Tensor, marlin_q: torch.Tensor, marlin_sca
 
 
 # ---------------------------------------------------------------------------------------------------------
-# CDNA4-native W4A16 (extension; layout contract in include/nmx.h): GPTQ checkpoint tensors repacked once into the order the
-# gfx950 MFMA consumes, and the GEMM on it. 4-bit symmetric, fp16 / bf16, K % 128 == 0, N % 64 == 0, channel-wise or 128-k groups.
+# CDNA4-native W4A16 / W8A16 (extension; layout contract in include/nmx.h): GPTQ checkpoint tensors repacked once into the order the
+# gfx950 MFMA consumes, and the GEMM on it. 4- or 8-bit symmetric (num_bits), fp16 / bf16, K % 128 == 0, N % 64 == 0, channel-wise
+# or 128-k groups. num_bits = 8 routes the same ops to the nmx_w8a16_* entries.
 # ---------------------------------------------------------------------------------------------------------
 def w4a16_supported(size_n: int, size_k: int, num_groups: int, num_bits: int = 4, has_act_order: bool = False) -> bool:
     return bool(_lib.lib().nmx_w4a16_supported(c_int(size_n), c_int(size_k), c_int(num_groups), c_int(num_bits),
                                                c_int(int(has_act_order))))
 
 
-def w4a16_repack(qweight: torch.Tensor, scales: torch.Tensor):
-    """GPTQ checkpoint qweight [K / 8, N] int32 + scales [G, N] -> (qweight_native [K / 128, 16 N] int32, scales_native [G, N])."""
+def _w4a16_entry(name: str, num_bits: int):
+    if num_bits not in (4, 8):
+        raise RuntimeError(f"w4a16: num_bits = {num_bits}, 4 or 8 expected")
+    return getattr(_lib.lib(), f"nmx_w{num_bits}a16_{name}")
+
+
+def w4a16_repack(qweight: torch.Tensor, scales: torch.Tensor, num_bits: int = 4):
+    """GPTQ checkpoint qweight [K / pack, N] int32 (pack = 32 // num_bits) + scales [G, N] -> (qweight_native [K / 128,
+    (128 / pack) N] int32 - 16 N at 4 bits, 32 N at 8 -, scales_native [G, N])."""
     _dev(qweight)
+    entry = _w4a16_entry("repack", num_bits)
+    pack = 32 // num_bits
     if qweight.dtype != torch.int32 or qweight.dim() != 2 or scales.dim() != 2 or scales.shape[1] != qweight.shape[1]:
-        raise RuntimeError("w4a16_repack: qweight [K / 8, N] int32 and scales [G, N] expected")
+        raise RuntimeError(f"w4a16_repack: qweight [K / {pack}, N] int32 and scales [G, N] expected")
     if not (qweight.is_contiguous() and scales.is_contiguous() and scales.is_cuda):
         raise RuntimeError("w4a16_repack: contiguous GPU tensors expected")
-    k, n = qweight.shape[0] * 8, qweight.shape[1]
-    out_q = torch.empty((max(k // 128, 0), n * 16), dtype=torch.int32, device=qweight.device)
+    k, n = qweight.shape[0] * pack, qweight.shape[1]
+    out_q = torch.empty((max(k // 128, 0), n * (128 // pack)), dtype=torch.int32, device=qweight.device)
     out_s = torch.empty_like(scales)
-    _lib.check(_lib.lib().nmx_w4a16_repack(_p(qweight), _p(scales), _p(out_q), _p(out_s), c_int(k), c_int(n),
-                                           c_int(scales.shape[0]), c_int(_dt(scales)), _stream(qweight)))
+    _lib.check(entry(_p(qweight), _p(scales), _p(out_q), _p(out_s), c_int(k), c_int(n), c_int(scales.shape[0]),
+                     c_int(_dt(scales)), _stream(qweight)))
     return out_q, out_s
 
 
-def _w4a16_call(entry: str, a, qweight_native, scales_native, size_m, size_n, size_k, *tail):
+def _w4a16_call(entry: str, num_bits: int, a, qweight_native, scales_native, size_m, size_n, size_k, *tail):
     _dev(a)
+    fn, pack = _w4a16_entry(entry, num_bits), 32 // num_bits
     if a.dim() != 2 or a.shape[0] != size_m or a.shape[1] != size_k or not a.is_contiguous():
         raise RuntimeError(f"w4a16_gemm: a must be a contiguous [size_m = {size_m}, size_k = {size_k}] tensor, got {tuple(a.shape)}")
-    if qweight_native.dtype != torch.int32 or qweight_native.numel() * 8 != size_k * size_n or not qweight_native.is_contiguous():
-        raise RuntimeError(f"w4a16_gemm: qweight_native must hold size_k * size_n / 8 = {size_k * size_n // 8} int32 words")
+    if qweight_native.dtype != torch.int32 or qweight_native.numel() * pack != size_k * size_n or not qweight_native.is_contiguous():
+        raise RuntimeError(f"w4a16_gemm: qweight_native must hold size_k * size_n / {pack} = {size_k * size_n // pack} int32 words")
     if scales_native.dtype != a.dtype or scales_native.dim() != 2 or scales_native.shape[1] != size_n or not scales_native.is_contiguous():
         raise RuntimeError("w4a16_gemm: scales_native [G, size_n] must have the dtype of a")
     c = torch.empty((size_m, size_n), dtype=a.dtype, device=a.device)
-    need = _lib.lib().nmx_w4a16_gemm_scratch_bytes(c_int(size_m), c_int(size_n), c_int(size_k))
+    need = _w4a16_entry("gemm_scratch_bytes", num_bits)(c_int(size_m), c_int(size_n), c_int(size_k))
     scratch = _get_scratch(a.device, int(need))
-    _lib.check(getattr(_lib.lib(), entry)(_p(a), _p(qweight_native), _p(scales_native), _p(c), _p(scratch), c_i64(scratch.numel()),
-                                          c_int(size_m), c_int(size_n), c_int(size_k), c_int(scales_native.shape[0]),
-                                          c_int(_dt(a)), *tail, _stream(a)))
+    _lib.check(fn(_p(a), _p(qweight_native), _p(scales_native), _p(c), _p(scratch), c_i64(scratch.numel()), c_int(size_m),
+                  c_int(size_n), c_int(size_k), c_int(scales_native.shape[0]), c_int(_dt(a)), *tail, _stream(a)))
     return c, scratch
 
 
 def w4a16_gemm(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor, size_m: int, size_n: int,
-               size_k: int) -> torch.Tensor:
-    return _w4a16_call("nmx_w4a16_gemm", a, qweight_native, scales_native, size_m, size_n, size_k)[0]
+               size_k: int, num_bits: int = 4) -> torch.Tensor:
+    return _w4a16_call("gemm", num_bits, a, qweight_native, scales_native, size_m, size_n, size_k)[0]
 
 
-def w4a16_gemm_plan(size_m: int, size_n: int, size_k: int):
+def w4a16_gemm_plan(size_m: int, size_n: int, size_k: int, num_bits: int = 4):
     """(mt, nw, splits) that w4a16_gemm launches for this shape under the current NMX_W4A16 override: mt 16-row tiles per
-    workgroup (8 = the tall kernel), nw waves of the mt = 1 form (4 otherwise), splits K splits across workgroups."""
+    workgroup (8 = the tall kernel, 4 bits only), nw waves of the mt = 1 form (4 otherwise), splits K splits across workgroups."""
     mt, nw, splits = c_int(0), c_int(0), c_int(0)
-    _lib.check(_lib.lib().nmx_w4a16_gemm_plan(c_int(size_m), c_int(size_n), c_int(size_k), ctypes.byref(mt), ctypes.byref(nw),
-                                              ctypes.byref(splits)))
+    _lib.check(_w4a16_entry("gemm_plan", num_bits)(c_int(size_m), c_int(size_n), c_int(size_k), ctypes.byref(mt), ctypes.byref(nw),
+                                                   ctypes.byref(splits)))
     return mt.value, nw.value, splits.value
 
 
 def w4a16_gemm_deferred(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor, size_m: int, size_n: int,
-                        size_k: int) -> DeferredGemm:
+                        size_k: int, num_bits: int = 4) -> DeferredGemm:
     """w4a16_gemm whose split-K partial sums are left for the consumer op, like gptq_marlin_gemm_deferred."""
     splits = c_int(1)
-    c, scratch = _w4a16_call("nmx_w4a16_gemm_deferred", a, qweight_native, scales_native, size_m, size_n, size_k,
+    c, scratch = _w4a16_call("gemm_deferred", num_bits, a, qweight_native, scales_native, size_m, size_n, size_k,
                              ctypes.byref(splits))
     if (splits.value & 0xff) > 1:
         partial, n = _slabs(scratch, splits.value, size_m, size_n)

@@ -74,6 +74,18 @@ __device__ __forceinline__ u32x4 w4_fragment(uint32_t w, uint32_t magic) {
   }
 }
 
+// element o of scales_native (shared by the 4- and the 8-bit repack)
+__device__ __forceinline__ void repack_scale(int64_t o, const uint16_t* __restrict__ scales, uint16_t* __restrict__ snative, int N,
+                                             int G) {
+  if (o < (int64_t)G * N) {
+    const int C = N / 64;
+    const int j = (int)(o & 3), t = (int)(o >> 2) & 3, g = (int)(o >> 4) & 3;
+    const int64_t gc = o >> 6;
+    const int c = (int)(gc % C), grp = (int)(gc / C);
+    snative[o] = scales[(int64_t)grp * N + 64 * c + 16 * t + 4 * g + j];
+  }
+}
+
 // ---- repack: GPTQ checkpoint qweight [K / 8, N] (code k % 8 of row k / 8 at bits 4 (k % 8)) + scales [G, N] -> the native pair.
 // Native word (u, c, s, 16 g + r, t) is checkpoint word (16 u + 4 s + g, 64 c + 16 t + r) with its nibbles moved j -> P[j].
 __global__ void w4a16_repack_kernel(const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
@@ -92,12 +104,7 @@ __global__ void w4a16_repack_kernel(const uint32_t* __restrict__ qweight, const 
     for (int j = 0; j < 8; ++j) r |= ((w >> (4 * j)) & 0xfu) << (4 * ((j >> 1) + 4 * (j & 1)));
     qnative[o] = r;
   }
-  if (o < (int64_t)G * N) {
-    const int j = (int)(o & 3), t = (int)(o >> 2) & 3, g = (int)(o >> 4) & 3;
-    const int64_t gc = o >> 6;
-    const int c = (int)(gc % C), grp = (int)(gc / C);
-    snative[o] = scales[(int64_t)grp * N + 64 * c + 16 * t + 4 * g + j];
-  }
+  repack_scale(o, scales, snative, N, G);
 }
 
 // ---- the GEMM. c [M, N] = a [M, K] . W, W[k, n] = (q - 8) * s[group(k), n].
@@ -546,6 +553,299 @@ __global__ __launch_bounds__(256, 1) void w4a16_tall_kernel(const W4Params p) {
   }
 }
 
+// ======== 8 bits (include/nmx.h "8-bit form") ===========================================================
+//   qweight_native  int32 [K / 128][N / 64][step s = 0..3][half h = 0..1][lane l = 16 g + r][word 2 (t & 1) + j], tile t = 2 h + ..
+//       word (u, c, s, h, l, 2 (t & 1) + j) = the 4 codes of column n = 64 c + 16 t + r at k = 128 u + 32 s + 8 g + 4 j + i, code i
+//       in byte i: it IS checkpoint word (32 u + 8 s + 2 g + j, n) - the repack only moves words. A lane's 16 bytes = the two
+//       complete A fragments of tiles 2 h, 2 h + 1 for one 32-k step: two loads per lane and step, 8 KiB per unit and group.
+//   scales_native as above. W[k, n] = (q - 128) * s[group(k), n].
+
+// Two words -> the lane's A fragment (8 values q - 128, exact), no shift. fp16: v_perm_b32 against 0x64 bytes makes the pair
+// (1024 + b0, 1024 + b1), one v_pk_add_f16 of -1152 finishes it: 4 + 4 = 8 VALU. bf16 (no packed arithmetic; 0x4300 | b holds 7
+// bits): v_cvt_f32_ubyteN, minus 128, v_cvt_pk_bf16_f32 per pair = 20 VALU; q - 128 has 8 significant bits, exact in bf16.
+// (as asm: written as (float)(byte) - 128.f the subtraction is folded into integer SDWA adds and the pairs are re-packed by hand,
+// about 30 VALU per fragment)
+template <int B>
+__device__ __forceinline__ float ubyte_f32(uint32_t w) {
+  float f;
+  if constexpr (B == 0) asm("v_cvt_f32_ubyte0 %0, %1" : "=v"(f) : "v"(w));
+  else if constexpr (B == 1) asm("v_cvt_f32_ubyte1 %0, %1" : "=v"(f) : "v"(w));
+  else if constexpr (B == 2) asm("v_cvt_f32_ubyte2 %0, %1" : "=v"(f) : "v"(w));
+  else asm("v_cvt_f32_ubyte3 %0, %1" : "=v"(f) : "v"(w));
+  return f;
+}
+
+template <typename scalar_t, int H>  // pair H = bytes 2 H, 2 H + 1 of w
+__device__ __forceinline__ uint32_t w8_pair(uint32_t w) {
+  if constexpr (__is_same(scalar_t, f16)) {
+    const f16x2 n1152 = __builtin_bit_cast(f16x2, 0xe480e480u);
+    const uint32_t pair = __builtin_amdgcn_perm(0x64646464u, w, H ? 0x04030402u : 0x04010400u);
+    return __builtin_bit_cast(uint32_t, __builtin_bit_cast(f16x2, pair) + n1152);
+  } else {
+    union { bf16 h[2]; uint32_t u; } pk;
+    pk.h[0] = (bf16)(ubyte_f32<2 * H>(w) - 128.f);
+    pk.h[1] = (bf16)(ubyte_f32<2 * H + 1>(w) - 128.f);
+    return pk.u;
+  }
+}
+
+template <typename scalar_t>
+__device__ __forceinline__ u32x4 w8_fragment(uint32_t w0, uint32_t w1) {
+  return u32x4{w8_pair<scalar_t, 0>(w0), w8_pair<scalar_t, 1>(w0), w8_pair<scalar_t, 0>(w1), w8_pair<scalar_t, 1>(w1)};
+}
+
+// Native word o is checkpoint word (32 u + 8 s + 2 g + j, 64 c + 16 t + r), unchanged.
+__global__ void w8a16_repack_kernel(const uint32_t* __restrict__ qweight, const uint16_t* __restrict__ scales,
+                                    uint32_t* __restrict__ qnative, uint16_t* __restrict__ snative, int K, int N, int G) {
+  const int64_t o = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int C = N / 64;
+  if (o < (int64_t)(K / 4) * N) {
+    const int j = (int)(o & 1), t = 2 * ((int)(o >> 8) & 1) + ((int)(o >> 1) & 1), l = (int)(o >> 2) & 63, s = (int)(o >> 9) & 3;
+    const int64_t uc = o >> 11;
+    const int c = (int)(uc % C), u = (int)(uc / C);
+    const int kk = 32 * u + 8 * s + 2 * (l >> 4) + j, n = 64 * c + 16 * t + (l & 15);
+    qnative[o] = qweight[(int64_t)kk * N + n];
+  }
+  repack_scale(o, scales, snative, N, G);
+}
+
+// ---- the 8-bit GEMM: the forms, epilogues, K slabs and workgroup mapping of w4a16_gemm_kernel (above) on twice the weight
+// bytes. Weight stream: a ring of ONE unit = 8 dwordx4 registers per lane (4 steps x 2 halves, 32 VGPRs - what the 4-bit kernel
+// holds for two units); a half is converted, fed to its 2 MT MFMAs and re-issued for the next unit at once, so a wave keeps 8 KiB
+// of weights in flight, the same bytes as the 4-bit kernel's two units. The last unit of a slice is peeled and re-issues nothing:
+// no weight byte is read twice or past the slice. Staged: the two LDS images alternate by a run-time offset (one unit per trip).
+template <typename scalar_t, int MT, int NW, bool GROUPED, bool STAGED>
+__global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w8a16_gemm_kernel(const W4Params p) {
+  static_assert(STAGED ? NW == 4 : MT == 1, "staged: 4 waves = 4 column groups; unstaged: one 16-row tile");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int g = lane >> 4, r = lane & 15;
+  const int N = p.N, K = p.K, M = p.M;
+  const int C = N / 64, total_units = K / 128;
+
+  const int ncolwg = STAGED ? (C + 3) / 4 : C;
+  int colwg, split;
+  if (p.xcd_per > 0) {  // as w4a16_gemm_kernel: the XCD selects the K split
+    const int lin = blockIdx.x;
+    split = (lin & 7) / p.xcd_per;
+    colwg = (lin >> 3) * p.xcd_per + (lin & 7) % p.xcd_per;
+  } else {
+    colwg = blockIdx.x;
+    split = blockIdx.y;
+  }
+  if (colwg >= ncolwg) return;  // padding workgroup (whole workgroup: no barrier is skipped)
+  const int cg = STAGED ? colwg * 4 + wave : colwg;
+  const bool col_ok = cg < C;
+  const int cl = min(cg, C - 1);  // a wave past N computes a valid group again, never stored
+  const int m0 = blockIdx.z * (16 * MT);
+
+  constexpr int SLICES = STAGED ? 1 : NW;
+  const int workers = p.k_splits * SLICES;
+  const int per = (total_units + workers - 1) / workers;
+  const int worker = split * SLICES + (STAGED ? 0 : wave);
+  const int u0 = min(worker * per, total_units), u1 = min(u0 + per, total_units);
+
+  const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<int32_t*>(p.qw), 0, K * N, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_a = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.a), 0, M * K * 2, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_s = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.scales), 0, p.num_groups * N * 2, 0x00020000);
+  const int unit_bytes = C * 8192;  // one 128-k unit of all column groups
+  const int w_voff = cl * 8192 + lane * 16;
+  const int s_voff = (cl * 4 + g) * 32;
+  constexpr int kPast = 0x7ff00000;  // beyond every descriptor: the load returns zeros
+  int a_voff[STAGED ? MT : 1], a_lds[STAGED ? MT : 1];
+  if constexpr (STAGED) {  // chunk e = tid + 256 i of the tile image (row e >> 4, 16-byte chunk e & 15)
+#pragma unroll
+    for (int i = 0; i < MT; ++i) {
+      const int e = threadIdx.x + 256 * i, row = e >> 4, ch = e & 15;
+      a_voff[i] = (m0 + row < M) ? ((m0 + row) * K + 8 * ch) * 2 : kPast;
+      a_lds[i] = row * 256 + ((ch ^ (row & 15)) * 16);
+    }
+  } else {
+    a_voff[0] = (m0 + r < M) ? ((m0 + r) * K + 8 * g) * 2 : kPast;
+    a_lds[0] = 0;
+  }
+
+  constexpr int kTile = MT * 4096;  // staged activation image of one unit
+  __shared__ __attribute__((aligned(16))) char smem[STAGED ? 2 * kTile : NW * 4096];
+
+  u32x4 q[4][2], areg[STAGED ? MT : 4], sc[2];  // the ring; activations (unstaged: the unit's B fragments); the unit's scale row
+  // the loads of unit u (always inside the slice), queued in one order by prologue and loop (sched_barrier pins it)
+  auto load_half = [&](int u, int ks, int h) {
+    q[ks][h] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, w_voff, u * unit_bytes + ks * 2048 + h * 1024, 2);  // aux 2: non-temporal
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto load_a = [&](int u, int ks) {
+    if constexpr (!STAGED) {
+      areg[ks] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_voff[0], (u * 128 + ks * 32) * 2, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto load_scales = [&](int u) {
+    if constexpr (GROUPED) {  // one group per unit
+      sc[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, u * N * 2, 0);
+      sc[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, u * N * 2, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto stage_load = [&](int u) {
+    if constexpr (STAGED) {
+      u = min(u, total_units - 1);  // a unit past the slice: fetched again, never read
+#pragma unroll
+      for (int i = 0; i < MT; ++i) areg[i] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_voff[i], u * 256, 0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  auto stage_store = [&](char* buf) {
+    if constexpr (STAGED) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i) *reinterpret_cast<u32x4*>(buf + a_lds[i]) = areg[i];
+    }
+  };
+
+  f32x4 acc[MT][4];
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+    for (int t = 0; t < 4; ++t) acc[mt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // consumes the ring (activations: areg, or the LDS image buf); reissue: every register set is loaded for unit `next` as soon
+  // as it is free
+  auto compute_unit = [&](int next, const char* buf, bool reissue) {
+    f32x4 gacc[GROUPED ? MT : 1][4];
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      u32x4 bf[MT];
+      if constexpr (STAGED) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+          bf[mt] = *reinterpret_cast<const u32x4*>(buf + (16 * mt + r) * 256 + (((4 * ks + g) ^ r) * 16));
+      } else {
+        bf[0] = areg[ks];
+      }
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+#pragma unroll
+        for (int t = 2 * h; t < 2 * h + 2; ++t) {
+          const u32x4 wf = w8_fragment<scalar_t>(q[ks][h][2 * (t & 1)], q[ks][h][2 * (t & 1) + 1]);
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) {
+            if constexpr (GROUPED) gacc[mt][t] = mfma_w4<scalar_t>(wf, bf[mt], ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : gacc[mt][t]);
+            else acc[mt][t] = mfma_w4<scalar_t>(wf, bf[mt], acc[mt][t]);
+          }
+        }
+        if (reissue) load_half(next, ks, h);
+      }
+      if (reissue) load_a(next, ks);
+    }
+    if constexpr (GROUPED) {
+      union { u32x4 v[2]; scalar_t e[16]; } raw;
+      raw.v[0] = sc[0];
+      raw.v[1] = sc[1];
+#pragma unroll
+      for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float sv = Scalar<scalar_t>::to_f32(raw.e[4 * t + j]);
+#pragma unroll
+          for (int mt = 0; mt < MT; ++mt) acc[mt][t][j] = __builtin_fmaf(sv, gacc[mt][t][j], acc[mt][t][j]);
+        }
+      if (reissue) load_scales(next);
+    }
+  };
+
+  if (u0 < u1) {
+    stage_load(u0);
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+      load_half(u0, ks, 0);
+      load_half(u0, ks, 1);
+      load_a(u0, ks);
+    }
+    load_scales(u0);
+    int cur = 0;  // the image this unit reads; the other one is written for the next
+    if constexpr (STAGED) {
+      stage_store(smem);
+      stage_load(u0 + 1);
+      __syncthreads();
+    }
+    // A unit reads the image written before the previous barrier and writes the other one, which every wave finished reading
+    // before that same barrier.
+    int u = u0;
+    for (; u + 1 < u1; ++u) {
+      compute_unit(u + 1, smem + cur, true);
+      if constexpr (STAGED) {
+        cur ^= kTile;
+        stage_store(smem + cur);
+        stage_load(u + 2);
+        __syncthreads();
+      }
+    }
+    compute_unit(u, smem + cur, false);
+  }
+
+  // ---- epilogue (as w4a16_gemm_kernel) ----
+  scalar_t* const cptr = reinterpret_cast<scalar_t*>(p.c);
+  if constexpr (STAGED) {
+    if (!col_ok) return;
+    union { u32x4 v[2]; scalar_t e[16]; } cs;
+    if constexpr (!GROUPED) {
+      cs.v[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, 0, 0);
+      cs.v[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, 0, 0);
+    }
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt) {
+      const int m = m0 + 16 * mt + r;
+      if (m >= M) continue;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        f32x4 v = acc[mt][t];
+        if constexpr (!GROUPED) {
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[j] *= Scalar<scalar_t>::to_f32(cs.e[4 * t + j]);
+        }
+        const int64_t off = (int64_t)m * N + cg * 64 + 16 * t + 4 * g;
+        if (p.k_splits == 1) {
+          union { scalar_t h[4]; u32x2 u; } o;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o.h[j] = Scalar<scalar_t>::from_f32(v[j]);
+          *reinterpret_cast<u32x2*>(cptr + off) = o.u;
+        } else {
+          *reinterpret_cast<f32x4*>(p.partial + (int64_t)split * M * N + off) = v;
+        }
+      }
+    }
+  } else {
+    // sum the NW K slices through LDS: thread e < 256 owns float4 e of the workgroup's [4 tiles][64 lanes] image
+    f32x4* red = reinterpret_cast<f32x4*>(smem);
+#pragma unroll
+    for (int t = 0; t < 4; ++t) red[(wave * 4 + t) * 64 + lane] = acc[0][t];
+    __syncthreads();
+    for (int e = threadIdx.x; e < 256; e += 64 * NW) {
+      f32x4 v = red[e];
+#pragma unroll
+      for (int w = 1; w < NW; ++w) v += red[w * 256 + e];
+      const int t = e >> 6, el = e & 63, eg = el >> 4;
+      const int m = m0 + (el & 15);
+      if (m >= M) continue;
+      if constexpr (!GROUPED) {
+        union { u32x2 u; scalar_t e[4]; } cs;
+        cs.u = *reinterpret_cast<const u32x2*>(reinterpret_cast<const scalar_t*>(p.scales) + (cg * 4 + eg) * 16 + 4 * t);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] *= Scalar<scalar_t>::to_f32(cs.e[j]);
+      }
+      const int64_t off = (int64_t)m * N + cg * 64 + 16 * t + 4 * eg;
+      if (p.k_splits == 1) {
+        union { scalar_t h[4]; u32x2 u; } o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o.h[j] = Scalar<scalar_t>::from_f32(v[j]);
+        *reinterpret_cast<u32x2*>(cptr + off) = o.u;
+      } else {
+        *reinterpret_cast<f32x4*>(p.partial + (int64_t)split * M * N + off) = v;
+      }
+    }
+  }
+}
+
 // ---- dispatch --------------------------------------------------------------------------------------------------------
 // mt: 16-row tiles per workgroup (1: the unstaged form, 2 / 4: staged, 8: the tall kernel), nw: waves of the unstaged form
 // (4 / 8), splits: K splits across workgroups - only to fill the 256 CUs, and only while every wave keeps >= 2 units (the tall
@@ -592,17 +892,63 @@ int w4_launch(const W4Params& p, const W4Cfg& cfg, hipStream_t stream) {
   return NMX_OK;
 }
 
-int w4_common(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+// The 8-bit dispatch: w4_pick's rules (same override, same split rule) without the tall form - a forced mt = 8 falls to 4.
+W4Cfg w8_pick(int M, int N, int K) {
+  W4Cfg c;
+  // Thresholds in weight BYTES (K * N at 8 bits). Measured (tools/lean_sweep.py, LEAN_SWEEP_BITS=8, Llama-3-8B shapes, fp16 group
+  // 128, M = 1 / 16 / 64; DESIGN.md 3.1n8, profiles/w8a16_native_ab.txt): M = 1 the unstaged form everywhere; M = 16 the 24 MiB
+  // threshold carried over from w4_pick holds (o, 16 MiB: MT = 1 5.5 vs 6.3 us; qkv, 24 MiB: level; down, gate_up: MT = 2 12.7 vs
+  // 13.0, 20.5 vs 23.4); M = 64 two 32-row blocks win up to down's 56 MiB (qkv 11.2 vs 11.7, o 8.3 vs 9.7, down 17.6 vs 18.0 -
+  // 18.9) and MT = 4 on gate_up's 112 MiB (29.5 vs 31.5): the threshold there is put at 64 MiB. M = 8 and 32 are carried over
+  // from w4_pick, not measured.
+  const int64_t bytes = (int64_t)K * N;
+  const bool big = bytes >= (24ll << 20);
+  c.mt = M <= 8 ? 1 : (M <= 16 ? (big ? 2 : 1) : (M <= 32 ? 2 : (M <= 64 && bytes < (64ll << 20) ? 2 : 4)));
+  c.nw = 4;
+  c.splits = 1;
+  int f_mt = 0, f_nw = 0, f_splits = 0;
+  if (const char* e = nmx_tune(NMX_TUNE_W4A16)) sscanf(e, "%d,%d,%d", &f_mt, &f_nw, &f_splits);
+  if (f_mt == 1 || f_mt == 2 || f_mt == 4) c.mt = f_mt;
+  if (f_mt == 8) c.mt = 4;  // no 128-row form at 8 bits
+  if (c.mt == 1 && f_nw == 8) c.nw = 8;
+  const int units = K / 128, groups = N / 64;
+  const int row_blocks = ceil_div(M, 16 * c.mt);
+  const int wgs = (c.mt == 1 ? groups : ceil_div(groups, 4)) * row_blocks;
+  const int slices = c.mt == 1 ? c.nw : 1;
+  while (wgs * c.splits * 2 <= 256 && units / (slices * c.splits * 2) >= 2 && c.splits < 16) c.splits *= 2;
+  // 8 waves where the 4-wave grid already has a workgroup or more per CU and so gets no K split: twice the weight bytes in flight
+  // per CU (measured on gate_up at M = 1 only: 19.7 vs 21.1 us; with a K split, as on qkv / o / down, 4 waves win)
+  if (c.mt == 1 && f_nw == 0 && c.splits == 1 && wgs >= 256 && units >= 16) c.nw = 8;
+  if (f_splits >= 1) c.splits = f_splits;
+  c.splits = std::max(1, std::min(std::min(c.splits, units), 64));
+  return c;
+}
+
+template <typename scalar_t, bool GROUPED>
+int w8_launch(const W4Params& p, const W4Cfg& cfg, hipStream_t stream) {
+  const int C = p.N / 64;
+  const int ncolwg = cfg.mt == 1 ? C : ceil_div(C, 4);
+  dim3 grid(ncolwg, p.k_splits, ceil_div(p.M, 16 * cfg.mt));
+  if (p.xcd_per > 0) grid = dim3(ceil_div(ncolwg, p.xcd_per) * 8, 1, grid.z);
+  if (cfg.mt == 1 && cfg.nw == 8) w8a16_gemm_kernel<scalar_t, 1, 8, GROUPED, false><<<grid, 512, 0, stream>>>(p);
+  else if (cfg.mt == 1) w8a16_gemm_kernel<scalar_t, 1, 4, GROUPED, false><<<grid, 256, 0, stream>>>(p);
+  else if (cfg.mt == 2) w8a16_gemm_kernel<scalar_t, 2, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
+  else w8a16_gemm_kernel<scalar_t, 4, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
+  NMX_LAUNCH_CHECK();
+  return NMX_OK;
+}
+
+int w4_common(int bits, const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
               int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int defer,
               int* splits_out, hipStream_t stream) {
   if (splits_out != nullptr) *splits_out = 1;
   NMX_CHECK(dtype == NMX_F16 || dtype == NMX_BF16, NMX_ERR_UNSUPPORTED, "w4a16_gemm only supports bfloat16 and float16");
   NMX_CHECK(size_m >= 0 && size_n > 0 && size_k > 0, NMX_ERR_INVALID_ARG, "w4a16_gemm: size_m = %d, size_n = %d, size_k = %d", size_m,
             size_n, size_k);
-  NMX_CHECK(nmx_w4a16_supported(size_n, size_k, num_groups, 4, 0), NMX_ERR_UNSUPPORTED,
+  NMX_CHECK(nmx_w4a16_supported(size_n, size_k, num_groups, bits, 0), NMX_ERR_UNSUPPORTED,
             "w4a16_gemm: size_k = %d must be a multiple of 128, size_n = %d of 64, num_groups = %d one or size_k / 128", size_k, size_n,
             num_groups);
-  NMX_CHECK((int64_t)size_m * size_k * 2 <= 0x7ff00000ll && (int64_t)size_k * size_n < (1ll << 32) && (int64_t)size_m * size_n < (1ll << 31),
+  NMX_CHECK((int64_t)size_m * size_k * 2 <= 0x7ff00000ll && (int64_t)size_k * size_n * bits < (1ll << 34) && (int64_t)size_m * size_n < (1ll << 31),
             NMX_ERR_UNSUPPORTED, "w4a16_gemm: operand beyond the 2 GiB a buffer descriptor addresses");
   NMX_CHECK(a != nullptr && qweight_native != nullptr && scales_native != nullptr && c != nullptr, NMX_ERR_INVALID_ARG,
             "w4a16_gemm: null operand");
@@ -610,7 +956,7 @@ int w4_common(const void* a, const int32_t* qweight_native, const void* scales_n
                 ((uintptr_t)c % 8 == 0) && ((uintptr_t)scratch % 16 == 0),
             NMX_ERR_INVALID_ARG, "w4a16_gemm: operands must be 16-byte aligned");
   if (size_m == 0) return NMX_OK;
-  W4Cfg cfg = w4_pick(size_m, size_n, size_k);
+  W4Cfg cfg = bits == 8 ? w8_pick(size_m, size_n, size_k) : w4_pick(size_m, size_n, size_k);
   const int64_t slab = (int64_t)size_m * size_n * sizeof(float);
   if (scratch == nullptr) scratch_bytes = 0;
   if ((int64_t)cfg.splits * slab > scratch_bytes) cfg.splits = (int)std::max<int64_t>(1, scratch_bytes / slab);  // fewer splits, never past the scratch
@@ -621,7 +967,10 @@ int w4_common(const void* a, const int32_t* qweight_native, const void* scales_n
   const bool xcd = (xs == nullptr || atoi(xs) != 0) && (cfg.splits == 2 || cfg.splits == 4 || cfg.splits == 8);
   p.xcd_per = xcd ? 8 / cfg.splits : 0;
   int rc;
-  if (dtype == NMX_F16) rc = num_groups > 1 ? w4_launch<f16, true>(p, cfg, stream) : w4_launch<f16, false>(p, cfg, stream);
+  if (bits == 8) {
+    if (dtype == NMX_F16) rc = num_groups > 1 ? w8_launch<f16, true>(p, cfg, stream) : w8_launch<f16, false>(p, cfg, stream);
+    else rc = num_groups > 1 ? w8_launch<bf16, true>(p, cfg, stream) : w8_launch<bf16, false>(p, cfg, stream);
+  } else if (dtype == NMX_F16) rc = num_groups > 1 ? w4_launch<f16, true>(p, cfg, stream) : w4_launch<f16, false>(p, cfg, stream);
   else rc = num_groups > 1 ? w4_launch<bf16, true>(p, cfg, stream) : w4_launch<bf16, false>(p, cfg, stream);
   if (rc != NMX_OK || cfg.splits == 1) return rc;
   if (defer) {
@@ -634,7 +983,7 @@ int w4_common(const void* a, const int32_t* qweight_native, const void* scales_n
 }  // namespace
 
 extern "C" int nmx_w4a16_supported(int size_n, int size_k, int num_groups, int num_bits, int has_act_order) {
-  return num_bits == 4 && !has_act_order && size_n > 0 && size_k > 0 && size_k % 128 == 0 && size_n % 64 == 0 &&
+  return (num_bits == 4 || num_bits == 8) && !has_act_order && size_n > 0 && size_k > 0 && size_k % 128 == 0 && size_n % 64 == 0 &&
                  (num_groups == 1 || num_groups == size_k / 128)
              ? 1 : 0;
 }
@@ -676,7 +1025,7 @@ extern "C" int64_t nmx_w4a16_gemm_scratch_bytes(int size_m, int size_n, int size
 extern "C" int nmx_w4a16_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
                               int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
                               nmx_stream_t stream) {
-  return w4_common(a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 0, nullptr,
+  return w4_common(4, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 0, nullptr,
                    (hipStream_t)stream);
 }
 
@@ -684,6 +1033,56 @@ extern "C" int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_nat
                                        int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
                                        int* splits_out, nmx_stream_t stream) {
   NMX_CHECK(splits_out != nullptr, NMX_ERR_INVALID_ARG, "splits_out is null");
-  return w4_common(a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 1, splits_out,
+  return w4_common(4, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 1, splits_out,
+                   (hipStream_t)stream);
+}
+
+// ---- 8 bits: the same entries on the 8-bit form of the layout ----
+extern "C" int nmx_w8a16_repack(const int32_t* qweight, const void* scales, int32_t* qweight_native, void* scales_native,
+                                int size_k, int size_n, int num_groups, int dtype, nmx_stream_t stream) {
+  NMX_CHECK(dtype == NMX_F16 || dtype == NMX_BF16, NMX_ERR_UNSUPPORTED, "w8a16_repack only supports bfloat16 and float16 scales");
+  NMX_CHECK(nmx_w4a16_supported(size_n, size_k, num_groups, 8, 0), NMX_ERR_UNSUPPORTED,
+            "w8a16_repack: size_k = %d must be a multiple of 128, size_n = %d of 64, num_groups = %d one or size_k / 128", size_k, size_n,
+            num_groups);
+  NMX_CHECK(qweight != nullptr && scales != nullptr && qweight_native != nullptr && scales_native != nullptr &&
+                qweight != qweight_native && scales != scales_native,
+            NMX_ERR_INVALID_ARG, "w8a16_repack: null or aliased operand");
+  const int64_t words = (int64_t)(size_k / 4) * size_n;
+  w8a16_repack_kernel<<<(unsigned)ceil_div64(words, 256), 256, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const uint32_t*>(qweight), reinterpret_cast<const uint16_t*>(scales), reinterpret_cast<uint32_t*>(qweight_native),
+      reinterpret_cast<uint16_t*>(scales_native), size_k, size_n, num_groups);
+  NMX_LAUNCH_CHECK();
+  return NMX_OK;
+}
+
+extern "C" int nmx_w8a16_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits) {
+  NMX_CHECK(mt != nullptr && nw != nullptr && splits != nullptr, NMX_ERR_INVALID_ARG, "w8a16_gemm_plan: null output");
+  NMX_CHECK(size_m > 0 && size_n > 0 && size_k >= 128, NMX_ERR_INVALID_ARG, "w8a16_gemm_plan: size_m = %d, size_n = %d, size_k = %d", size_m,
+            size_n, size_k);
+  const W4Cfg c = w8_pick(size_m, size_n, size_k);
+  *mt = c.mt;
+  *nw = c.nw;
+  *splits = c.splits;
+  return NMX_OK;
+}
+
+extern "C" int64_t nmx_w8a16_gemm_scratch_bytes(int size_m, int size_n, int size_k) {
+  if (size_m <= 0 || size_n <= 0 || size_k < 128) return 0;
+  const int splits = w8_pick(size_m, size_n, size_k).splits;
+  return splits > 1 ? (int64_t)splits * size_m * size_n * sizeof(float) : 0;
+}
+
+extern "C" int nmx_w8a16_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                              int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
+                              nmx_stream_t stream) {
+  return w4_common(8, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 0, nullptr,
+                   (hipStream_t)stream);
+}
+
+extern "C" int nmx_w8a16_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
+                                       int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
+                                       int* splits_out, nmx_stream_t stream) {
+  NMX_CHECK(splits_out != nullptr, NMX_ERR_INVALID_ARG, "splits_out is null");
+  return w4_common(8, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 1, splits_out,
                    (hipStream_t)stream);
 }

@@ -1,9 +1,10 @@
-"""GPTQ checkpoints served through the CDNA4-native W4A16 layout (extension; no reference counterpart - the reference
+"""GPTQ checkpoints served through the CDNA4-native W4A16 / W8A16 layout (extension; no reference counterpart - the reference
 repacks GPTQ -> Marlin at load, gptq_marlin.py:330-420). Opt-in: `quantization="gptq_native"`.
 
 Same checkpoint keys and `create_weights` as GPTQMarlinConfig. The first `apply` repacks qweight / scales with
-`ops.w4a16_repack` where `ops.w4a16_supported` says yes (4 bits, channel-wise or 128-k groups, no act-order) and drops the
-checkpoint tensors; every other layer (8 bits, groups of 32 / 64, act-order) takes the parent's Marlin path unchanged."""
+`ops.w4a16_repack` where `ops.w4a16_supported` says yes (4 or 8 bits, channel-wise or 128-k groups, no act-order), remembers
+the bits on the layer and drops the checkpoint tensors; every other layer (groups of 32 / 64, act-order) takes the parent's
+Marlin path unchanged."""
 from typing import Optional
 
 import torch
@@ -41,7 +42,8 @@ class GPTQNativeLinearMethod(GPTQMarlinLinearMethod):
                                                  layer.scales.shape[0], cfg.weight_bits, cfg.desc_act)
         if not layer.w4a16_native:
             return super()._repack(layer)
-        qweight_native, scales_native = ops.w4a16_repack(layer.qweight, layer.scales)
+        layer.w4a16_bits = cfg.weight_bits
+        qweight_native, scales_native = ops.w4a16_repack(layer.qweight, layer.scales, num_bits=layer.w4a16_bits)
         replace_tensor(layer, "qweight", qweight_native)
         replace_tensor(layer, "scales", scales_native)
         layer.g_idx = None  # (no act-order on this path; qzeros stays on the meta device, as on the Marlin path)
@@ -57,7 +59,7 @@ class GPTQNativeLinearMethod(GPTQMarlinLinearMethod):
             return super().apply(layer, x, bias)
         reshaped_x = x.reshape(-1, x.shape[-1])
         output = ops.w4a16_gemm(reshaped_x, layer.qweight, layer.scales, reshaped_x.shape[0], layer.output_size_per_partition,
-                                layer.input_size_per_partition)
+                                layer.input_size_per_partition, num_bits=layer.w4a16_bits)
         if bias is not None:
             output.add_(bias)
         return output.reshape(x.shape[:-1] + (layer.output_size_per_partition, ))
@@ -69,7 +71,7 @@ class GPTQNativeLinearMethod(GPTQMarlinLinearMethod):
             return super().apply_silu_and_mul(layer, x)
         reshaped_x = x.reshape(-1, x.shape[-1])
         g = ops.w4a16_gemm_deferred(reshaped_x, layer.qweight, layer.scales, reshaped_x.shape[0], layer.output_size_per_partition,
-                                    layer.input_size_per_partition)
+                                    layer.input_size_per_partition, num_bits=layer.w4a16_bits)
         act = torch.empty((reshaped_x.shape[0], layer.output_size_per_partition // 2), dtype=x.dtype, device=x.device)
         ops.silu_and_mul_splitk(act, g)
         return act.reshape(x.shape[:-1] + (layer.output_size_per_partition // 2, ))

@@ -6,7 +6,9 @@ usage (GPU box): python3 tools/lean_sweep.py [M ...] > gpurun_out/lean_sweep.txt
 cfg strings: "D:auto" = default dispatch, "L:nw,splits[,mt[,ws]]" = marlin_decode_kernel, "G:ngrp" = marlin_large_kernel, "S:mt,ng,splits[,w8]" = marlin_gemm_kernel, "S:auto" its heuristic,
 "X:splits" = marlin_dma_kernel, "N:auto" / "N:mt,nw,splits" = w4a16_gemm on the CDNA4-native layout (NMX_W4A16; 0 = default; mt 1 / 2 / 4
 = w4a16_gemm_kernel, 8 = w4a16_tall_kernel), checked against the 64-row form "4,0,1" (the
-same random words mean other weights there than in Marlin's order); the line ends with the plan launched and its fp32 slab bytes."""
+same random words mean other weights there than in Marlin's order); the line ends with the plan launched and its fp32 slab bytes.
+LEAN_SWEEP_BITS=8 runs every family on 8-bit weights (Marlin: num_bits = 8; "N:": the 8-bit form of the native layout), so
+LEAN_SWEEP_ONLY="D:auto;N:auto;D:auto;N:auto" times the Marlin and the native 8-bit path alternately in one call."""
 import os
 import sys
 
@@ -21,6 +23,7 @@ if os.environ.get("LEAN_SWEEP_SET") == "kscan":  # gate_up's N at growing K: tim
 if os.environ.get("LEAN_SWEEP_SET") == "70b-tp8":  # one rank of Llama-3-70B at TP = 8 (bench.py LLAMA3_70B_TP8_RANK)
     SHAPES = {"qkv": (8192, 1280), "o": (1024, 8192), "gate_up": (8192, 7168), "down": (3584, 8192)}
 NL = 32
+BITS = int(os.environ.get("LEAN_SWEEP_BITS", "4"))
 dev = "cuda:0"
 
 
@@ -108,14 +111,14 @@ def main():
     for name, (K, N) in SHAPES.items():
         if only_shapes and name not in only_shapes.split(","):
             continue
-        ws = [(torch.randint(-2**31, 2**31 - 1, (K // 16, N * 2), dtype=torch.int32, device=dev, generator=g),
+        ws = [(torch.randint(-2**31, 2**31 - 1, (K // 16, N * BITS // 2), dtype=torch.int32, device=dev, generator=g),
                (torch.rand(K // 128, N, device=dev, generator=g) * 0.004 + 0.002).half()) for _ in range(NL)]
         for M in Ms:
             x = torch.randn(M, K, dtype=torch.float16, device=dev)
             set_cfg("S:auto")
-            ref = ops.gptq_marlin_gemm(x, ws[0][0], ws[0][1], e, e, wsp, 4, M, N, K, True).float()
+            ref = ops.gptq_marlin_gemm(x, ws[0][0], ws[0][1], e, e, wsp, BITS, M, N, K, True).float()
             torch.cuda.synchronize()
-            by = K * N // 2 + (K // 128) * N * 2 + 2 * M * K + 2 * M * N
+            by = K * N * BITS // 8 + (K // 128) * N * 2 + 2 * M * K + 2 * M * N
             only = os.environ.get("LEAN_SWEEP_ONLY")
             for cfg in (only.split(";") if only else cfgs_for(name, M)):
                 if cfg.startswith("T:"):  # yardstick only: dense fp16 torch.matmul (hipBLASLt) on 32 distinct fp16 weights of the shape
@@ -128,30 +131,30 @@ def main():
                     print(f"{'hipBLASLt-fp16':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {(2 * K * N + 2 * M * K + 2 * M * N) / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  (dense fp16 yardstick)", flush=True)
                     del dws
                     continue
-                if cfg.startswith("N:"):  # the native layout: the same 32 word tensors, viewed [K / 128, 16 N]
+                if cfg.startswith("N:"):  # the native layout: the same 32 word tensors, viewed [K / 128, 16 N] (8 bits: 32 N)
                     try:
-                        wn = [(w[0].view(K // 128, N * 16), w[1]) for w in ws]
+                        wn = [(w[0].view(K // 128, N * BITS * 4), w[1]) for w in ws]
                         set_cfg("N:4,0,1")
-                        nref = ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K).float()
+                        nref = ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K, num_bits=BITS).float()
                         set_cfg(cfg)
-                        mt, nw, splits = ops.w4a16_gemm_plan(M, N, K)
+                        mt, nw, splits = ops.w4a16_gemm_plan(M, N, K, num_bits=BITS)
                         slab = splits * M * N * 4 if splits > 1 else 0
-                        err = ((ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K).float() - nref).abs().mean() / nref.abs().mean()).item()
+                        err = ((ops.w4a16_gemm(x, wn[0][0], wn[0][1], M, N, K, num_bits=BITS).float() - nref).abs().mean() / nref.abs().mean()).item()
                         gemm = ops.w4a16_gemm_deferred if os.environ.get("LEAN_SWEEP_DEFER") == "1" else ops.w4a16_gemm
 
                         def run_n():
                             for w in wn:
-                                gemm(x, w[0], w[1], M, N, K)
+                                gemm(x, w[0], w[1], M, N, K, num_bits=BITS)
 
                         us = time_graph(run_n) / NL
-                        print(f"{'w4a16-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_native_mt4={err:.2e}  plan={mt},{nw},{splits} slab={slab}", flush=True)
+                        print(f"{f'w{BITS}a16-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_native_mt4={err:.2e}  plan={mt},{nw},{splits} slab={slab}", flush=True)
                     except Exception as ex:  # noqa: BLE001
                         print(f"{name:8} M={M:3d} {cfg:12} FAILED {ex}", flush=True)
                         torch.cuda.synchronize()
                     continue
                 set_cfg(cfg)
                 try:
-                    out = ops.gptq_marlin_gemm(x, ws[0][0], ws[0][1], e, e, wsp, 4, M, N, K, True).float()
+                    out = ops.gptq_marlin_gemm(x, ws[0][0], ws[0][1], e, e, wsp, BITS, M, N, K, True).float()
                     torch.cuda.synchronize()
                     err = ((out - ref).abs().mean() / ref.abs().mean()).item()
 
@@ -160,9 +163,9 @@ def main():
                     def run():
                         for w in ws:
                             if defer:
-                                ops.gptq_marlin_gemm_deferred(x, w[0], w[1], e, e, wsp, 4, M, N, K, True)
+                                ops.gptq_marlin_gemm_deferred(x, w[0], w[1], e, e, wsp, BITS, M, N, K, True)
                             else:
-                                ops.gptq_marlin_gemm(x, w[0], w[1], e, e, wsp, 4, M, N, K, True)
+                                ops.gptq_marlin_gemm(x, w[0], w[1], e, e, wsp, BITS, M, N, K, True)
 
                     us = time_graph(run) / NL
                     print(f"{os.environ.get('NMX_LIB_PATH', '').split('/')[-1]:18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_default={err:.2e}", flush=True)
