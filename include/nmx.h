@@ -527,6 +527,26 @@ int nmx_moe_mm(void* out, const void* a, const void* w, const float* topk_weight
                const int32_t* expert_ids, const int32_t* num_tokens_post_padded, int num_valid, int a_rows, int a_row_div, int n, int k,
                int num_experts, int block_rows, int max_blocks, int dtype, nmx_stream_t stream);
 
+/* int4 mixture-of-experts: the grouped GEMM on the CDNA4-native W4A16 layout (extension; the contract of the
+ * layout and of the arithmetic is that of nmx_w4a16_gemm above). qweight_native int32 [num_experts, k / 128, 16 n] and
+ * scales_native [num_experts, num_groups, n] are the outputs of nmx_w4a16_repack of every expert, stacked; 4 bits, fp16 / bf16,
+ * k % 128 == 0, n % 64 == 0, num_groups 1 or k / 128.
+ *   out[id, :] = cast((a[id / a_row_div, :] . W_e) * [topk_weights[id]]),  W_e[k, n] = (q_e[k, n] - 8) * s_e[group(k), n]
+ * for every id of every block of `block_rows` (16 or 64) entries of sorted_token_ids (entries >= num_valid are padding),
+ * e = expert_ids[block]; the routing weight (topk_weights may be null) multiplies the fp32 sum before the cast. a [a_rows, k],
+ * out [num_valid, n]; max_blocks = entries of expert_ids; blocks past num_tokens_post_padded[0] do nothing. With K splits
+ * (nmx_moe_w4a16_mm_plan; chosen from the arguments alone, NMX_MOE_W4A16 = "1" / "2" / "4" forces them) the fp32 partial sums go
+ * through `scratch` (nmx_moe_w4a16_mm_scratch_bytes; with less, fewer splits) and nmx_splitk_reduce writes out. Any other
+ * block_rows, an unsupported shape, or one expert's weights, a or out beyond the 2 GiB of a 32-bit buffer offset return an error
+ * and launch nothing. Nothing is read on the host: capturable. All entries only enqueue. */
+int nmx_moe_w4a16_mm(void* out, const void* a, const int32_t* qweight_native, const void* scales_native,
+                     const float* topk_weights, const int32_t* sorted_token_ids, const int32_t* expert_ids,
+                     const int32_t* num_tokens_post_padded, void* scratch, int64_t scratch_bytes, int num_valid, int a_rows,
+                     int a_row_div, int n, int k, int num_groups, int num_experts, int block_rows, int max_blocks, int dtype,
+                     nmx_stream_t stream);
+int64_t nmx_moe_w4a16_mm_scratch_bytes(int num_valid, int n, int k, int num_experts, int block_rows);
+int nmx_moe_w4a16_mm_plan(int num_valid, int n, int k, int num_experts, int block_rows, int* splits);
+
 /*
  * All-reduce over the xGMI mesh for decode-sized messages. Replaces the `_C_custom_ar` ops of the reference
  * (csrc/custom_all_reduce.cu: meta_size, init_custom_ar, register_buffer, should_custom_ar, all_reduce_reg, dispose; kernels

@@ -1405,6 +1405,50 @@ def moe_mm(out: torch.Tensor, a: torch.Tensor, w: torch.Tensor, topk_weights: Op
         c_int(expert_ids.numel()), c_int(_dt(out)), _stream(a)))
 
 
+def moe_w4a16_mm(out: torch.Tensor, a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor,
+                 topk_weights: Optional[torch.Tensor], sorted_token_ids: torch.Tensor, expert_ids: torch.Tensor,
+                 num_tokens_post_padded: torch.Tensor, a_row_div: int, block_rows: int) -> None:
+    """Grouped int4 GEMM over the expert-sorted (token, k) pairs on the CDNA4-native layout (extension; include/nmx.h):
+    out[id] = (a[id // a_row_div] @ W[expert]) * [topk_weights[id]], W[e][k, n] = (q - 8) * s[group(k), n].
+    a [rows, K], qweight_native [E, K / 128, 16 N] int32 and scales_native [E, G, N] (every expert's w4a16_repack, stacked),
+    out [num_valid, N]; a, scales and out of one dtype (fp16 / bf16). No host reads: graph-capturable."""
+    _dev(a)
+    if a.dtype not in (torch.float16, torch.bfloat16) or scales_native.dtype != a.dtype or out.dtype != a.dtype or \
+            not (a.is_contiguous() and qweight_native.is_contiguous() and scales_native.is_contiguous()):
+        raise RuntimeError("moe_w4a16_mm: a, scales_native and out must be contiguous float16 / bfloat16 tensors of one dtype")
+    if qweight_native.dtype != torch.int32 or qweight_native.dim() != 3 or scales_native.dim() != 3 or a.dim() != 2 or out.dim() != 2 or \
+            scales_native.shape[0] != qweight_native.shape[0] or not out.is_contiguous():
+        raise RuntimeError("moe_w4a16_mm: shapes a [rows, K], qweight_native [E, K / 128, 16 N] int32, scales_native [E, G, N], out [num_valid, N]")
+    e, groups, n = scales_native.shape
+    k = a.shape[1]
+    if out.shape[1] != n or k % 128 != 0 or tuple(qweight_native.shape) != (e, k // 128, 16 * n):
+        raise RuntimeError(f"moe_w4a16_mm: qweight_native {tuple(qweight_native.shape)} is not [E = {e}, K / 128, 16 N] for K = {k}, N = {n}, "
+                           f"or out has {out.shape[1]} columns")
+    for t in (sorted_token_ids, expert_ids, num_tokens_post_padded):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError("moe_w4a16_mm: index tensors must be contiguous int32")
+    tw = None
+    if topk_weights is not None:
+        tw = topk_weights.reshape(-1)
+        if tw.dtype != torch.float32 or not tw.is_contiguous() or tw.numel() != out.shape[0]:
+            raise RuntimeError("moe_w4a16_mm: topk_weights must be float32 with one entry per output row")
+    lib = _lib.lib()
+    need = lib.nmx_moe_w4a16_mm_scratch_bytes(c_int(out.shape[0]), c_int(n), c_int(k), c_int(e), c_int(block_rows))
+    scratch = _get_scratch(a.device, int(need))
+    _lib.check(lib.nmx_moe_w4a16_mm(
+        _p(out), _p(a), _p(qweight_native), _p(scales_native), _p(tw), _p(sorted_token_ids), _p(expert_ids),
+        _p(num_tokens_post_padded), _p(scratch), c_i64(scratch.numel()), c_int(out.shape[0]), c_int(a.shape[0]), c_int(a_row_div),
+        c_int(n), c_int(k), c_int(groups), c_int(e), c_int(block_rows), c_int(expert_ids.numel()), c_int(_dt(out)), _stream(a)))
+
+
+def moe_w4a16_mm_plan(num_valid: int, size_n: int, size_k: int, num_experts: int, block_rows: int) -> int:
+    """K splits that moe_w4a16_mm launches for this call under the current NMX_MOE_W4A16 override."""
+    splits = c_int(0)
+    _lib.check(_lib.lib().nmx_moe_w4a16_mm_plan(c_int(num_valid), c_int(size_n), c_int(size_k), c_int(num_experts), c_int(block_rows),
+                                                ctypes.byref(splits)))
+    return splits.value
+
+
 def topk_softmax(topk_weights: torch.Tensor, topk_ids: torch.Tensor, token_expert_indicies: torch.Tensor,
                  gating_output: torch.Tensor) -> None:
     _dev(gating_output)

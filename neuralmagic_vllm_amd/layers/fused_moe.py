@@ -115,6 +115,38 @@ def _fused_experts_half(hidden_states, w1, w2, topk_weights, topk_ids, inplace):
     return out
 
 
+def fused_experts_w4a16(hidden_states: torch.Tensor, w13_q: torch.Tensor, w13_s: torch.Tensor, w2_q: torch.Tensor,
+                        w2_s: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """fused_experts on int4 GPTQ experts held in the CDNA4-native W4A16 layout (extension; no reference counterpart): the pipeline
+    of _fused_experts_half with the grouped int4 GEMM (`moe_w4a16_mm`) in place of `moe_mm`. w13_q [E, H / 128, 16 * 2 I] int32 and
+    w13_s [E, G, 2 I] (gate | up), w2_q [E, I / 128, 16 H] and w2_s [E, G2, H]: every expert's `w4a16_repack`, stacked. Every step
+    is a device launch: graph-capturable."""
+    assert topk_weights.shape == topk_ids.shape, "topk shape mismatch"
+    assert hidden_states.is_contiguous() and hidden_states.dtype in (torch.float16, torch.bfloat16)
+    m, k = hidden_states.shape
+    e, _, n2 = w13_s.shape
+    h = w2_s.shape[2]
+    assert w13_q.shape[1] * 128 == k and h == k and w2_q.shape[1] * 128 == n2 // 2, "Hidden / intermediate size mismatch"
+    topk = topk_ids.shape[1]
+    dev, dt = hidden_states.device, hidden_states.dtype
+    numel = m * topk
+    block = 16 if numel <= 16 * e else 64  # as _fused_experts_half
+    max_sorted = numel + e * (block - 1)
+    sorted_ids = torch.empty(max_sorted, dtype=torch.int32, device=dev)
+    expert_ids = torch.empty((max_sorted + block - 1) // block, dtype=torch.int32, device=dev)
+    post_pad = torch.empty(1, dtype=torch.int32, device=dev)
+    ops.moe_align_block_size(topk_ids.contiguous(), e, block, sorted_ids, expert_ids, post_pad)
+    gate_up = torch.empty(numel, n2, dtype=dt, device=dev)
+    ops.moe_w4a16_mm(gate_up, hidden_states, w13_q, w13_s, None, sorted_ids, expert_ids, post_pad, topk, block)
+    inter = torch.empty(numel, n2 // 2, dtype=dt, device=dev)
+    ops.silu_and_mul(inter, gate_up)
+    out_rows = torch.empty(numel, h, dtype=dt, device=dev)
+    ops.moe_w4a16_mm(out_rows, inter, w2_q, w2_s, topk_weights.float().contiguous(), sorted_ids, expert_ids, post_pad, 1, block)
+    out = hidden_states if inplace else torch.empty_like(hidden_states)
+    torch.sum(out_rows.view(m, topk, h), dim=1, out=out)  # moe_sum
+    return out
+
+
 def _fused_experts_fp8(hidden_states, w1, w2, topk_weights, topk_ids, inplace, w1_scale, w2_scale, a1_scale, a2_scale):
     """fused_experts with use_fp8 (fused_moe.py:402-511): align -> quantise -> grouped GEMM (gate | up) -> silu_and_mul ->
     quantise -> grouped GEMM with the routing weight -> sum over k. Every step is a device launch."""
