@@ -150,6 +150,22 @@ int nmx_context_attention_fwd(void* out, const void* q, const void* k, const voi
                               int64_t v_stride_h, int64_t o_stride_t, int64_t o_stride_h, int64_t kc_stride_b,
                               int64_t kc_stride_h, int64_t vc_stride_b, int64_t vc_stride_h, int64_t bloc_stride,
                               int max_input_len, int sliding_window, float sm_scale, int dtype, nmx_stream_t stream);
+/* The same over a cache of kv_dtype (no reference counterpart: the reference's Triton kernel reads a 16-bit cache only, so
+ * a server with kv_cache_dtype="fp8" has no prefix caching or chunked prefill there). NMX_KV_AUTO is the call above.
+ * NMX_KV_FP8_E4M3 / NMX_KV_FP8_E5M2: the cache is the one-byte decode layout nmx_reshape_and_cache writes and
+ * nmx_paged_attention_v1 / v2 read - k_cache [NB, Hkv, D/16, BS, 16] (x = 16), v_cache [NB, Hkv, D, BS], element =
+ * fp8(value / kv_scale) - and the result is attention over float(fp8) * kv_scale plus the new tokens; q, k, v and out stay
+ * float16 / bfloat16. Cache strides in elements (= bytes): k_cache and its strides multiples of 16, v_cache and its strides
+ * multiples of 8; kv_scale > 0 (ignored for NMX_KV_AUTO). */
+int nmx_context_attention_fwd_kv(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                 const void* v_cache, const int32_t* b_loc, const int32_t* b_start_loc,
+                                 const int32_t* b_seq_len, const int32_t* b_ctx_len, const float* alibi_slopes, int batch,
+                                 int num_heads, int num_kv_heads, int head_size, int block_size, int x, int64_t q_stride_t,
+                                 int64_t q_stride_h, int64_t k_stride_t, int64_t k_stride_h, int64_t v_stride_t,
+                                 int64_t v_stride_h, int64_t o_stride_t, int64_t o_stride_h, int64_t kc_stride_b,
+                                 int64_t kc_stride_h, int64_t vc_stride_b, int64_t vc_stride_h, int64_t bloc_stride,
+                                 int max_input_len, int sliding_window, float sm_scale, int dtype, int kv_dtype,
+                                 float kv_scale, nmx_stream_t stream);
 
 /* reshape_and_cache (cache_kernels.cu:253-278). key/value [num_tokens, num_heads, head_size] with row strides in
  * elements; slot_mapping [num_tokens] int64, negative = padding token (skipped). fp8: stores fp8(val / kv_scale). */

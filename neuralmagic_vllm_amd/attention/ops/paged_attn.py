@@ -69,12 +69,15 @@ class PagedAttention:
     def forward_prefix(query: torch.Tensor, key: torch.Tensor, value: torch.Tensor, key_cache: torch.Tensor,
                        value_cache: torch.Tensor, block_tables: torch.Tensor, query_start_loc: torch.Tensor,
                        seq_lens_tensor: torch.Tensor, context_lens: torch.Tensor, max_query_len: int,
-                       alibi_slopes: Optional[torch.Tensor], sliding_window: Optional[int]) -> torch.Tensor:
-        """paged_attn.py:183-216 — prefill with a cached prefix (query_start_loc is [batch + 1])."""
+                       alibi_slopes: Optional[torch.Tensor], sliding_window: Optional[int],
+                       kv_cache_dtype: str = "auto", kv_scale: float = 1.0) -> torch.Tensor:
+        """paged_attn.py:183-216 — prefill with a cached prefix (query_start_loc is [batch + 1]). With an fp8
+        kv_cache_dtype the caches are the ones write_to_paged_cache / forward_decode use with the same kv_scale."""
         from neuralmagic_vllm_amd.attention.ops.prefix_prefill import context_attention_fwd
         output = torch.empty_like(query)
         context_attention_fwd(query, key, value, output, key_cache, value_cache, block_tables, query_start_loc[:-1],
-                              seq_lens_tensor, context_lens, max_query_len, alibi_slopes, sliding_window)
+                              seq_lens_tensor, context_lens, max_query_len, alibi_slopes, sliding_window, kv_cache_dtype,
+                              kv_scale)
         return output
 
     @staticmethod

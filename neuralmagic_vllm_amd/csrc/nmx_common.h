@@ -114,6 +114,35 @@ template <int KV> __device__ __forceinline__ uint8_t f32_to_fp8_sat(float f) {
   if constexpr (KV == NMX_KV_FP8_E4M3) return f32_to_fp8_e4m3_sat(f);
   else return f32_to_fp8_e5m2_sat(f);
 }
+// 8 fp8 bytes (two dwords) -> 8 scalar_t (four dwords, same order), no scale: every e4m3 / e5m2 value is exactly
+// representable in fp16 and bf16 (the paged-attention decode kernel and the fp8-cache prefill kernels)
+template <typename scalar_t, int KV>
+__device__ __forceinline__ u32x4 cvt8_fp8_exact(u32x2 w) {
+  // gfx950 converts two fp8 bytes straight into a packed fp16 / bf16 pair (v_cvt_scalef32_pk_{f16,bf16}_{fp8,bf8}, unit
+  // scale): one instruction per pair instead of fp8 -> f32 -> pack (the fp8-KV decode kernel was VALU-busy 68 %)
+  u32x4 r;
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    if constexpr (__is_same(scalar_t, f16)) {
+      if constexpr (KV == NMX_KV_FP8_E4M3) {
+        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, false));
+        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, true));
+      } else {
+        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w[i], 1.0f, false));
+        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w[i], 1.0f, true));
+      }
+    } else {
+      if constexpr (KV == NMX_KV_FP8_E4M3) {
+        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, false));
+        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, true));
+      } else {
+        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w[i], 1.0f, false));
+        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w[i], 1.0f, true));
+      }
+    }
+  }
+  return r;
+}
 
 // ---- wave-level reductions ------------------------------------------------------------------------------
 __device__ __forceinline__ float wave_reduce_max(float v) {

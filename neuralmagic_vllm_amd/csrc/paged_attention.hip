@@ -107,34 +107,7 @@ __device__ __forceinline__ u32x4 cvt8_fp8(u32x2 w, float scale) {
   return r;
 }
 
-// 8 fp8 bytes -> 8 scalar_t, no scale: every e4m3 / e5m2 value is exactly representable in fp16 and bf16
-template <typename scalar_t, int KV>
-__device__ __forceinline__ u32x4 cvt8_fp8_exact(u32x2 w) {
-  // gfx950 converts two fp8 bytes straight into a packed fp16 / bf16 pair (v_cvt_scalef32_pk_{f16,bf16}_{fp8,bf8}, unit
-  // scale): one instruction per pair instead of fp8 -> f32 -> pack (the fp8-KV decode kernel was VALU-busy 68 %)
-  u32x4 r;
-#pragma unroll
-  for (int i = 0; i < 2; ++i) {
-    if constexpr (__is_same(scalar_t, f16)) {
-      if constexpr (KV == NMX_KV_FP8_E4M3) {
-        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, false));
-        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[i], 1.0f, true));
-      } else {
-        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w[i], 1.0f, false));
-        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_f16_bf8(w[i], 1.0f, true));
-      }
-    } else {
-      if constexpr (KV == NMX_KV_FP8_E4M3) {
-        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, false));
-        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp8(w[i], 1.0f, true));
-      } else {
-        r[2 * i] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w[i], 1.0f, false));
-        r[2 * i + 1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_bf8(w[i], 1.0f, true));
-      }
-    }
-  }
-  return r;
-}
+// (cvt8_fp8_exact - 8 fp8 bytes -> 8 scalar_t at unit scale - lives in nmx_common.h: the prefill kernels share it)
 
 // Re-shape P from the MFMA C/D layout into the B-operand layout.
 // In : a = sub-tile 0, b = sub-tile 1; lane (g, q) holds tokens 4g..4g+3 of each (two packed dwords).

@@ -18,6 +18,10 @@
 // for tiles every row sees completely, exp2 with the scale folded into one fma, row reductions with
 // v_permlane{16,32}_swap, and a lazy running maximum (softmax_pv).
 // grid (num_heads [/ 2], batch, ceil(max_input_len / 64)), block 256.
+// Both kernels also read the context from an fp8 cache (K [NB, Hkv, D/16, BS, 16], V [NB, Hkv, D, BS], one byte per
+// element = fp8(value / kv_scale), the decode layout): the bytes are converted to scalar_t at unit scale - exact - on
+// their way into the same fragments, and kv_scale enters the softmax in fp32 (softmax_pv). Queries, new tokens and the
+// output stay scalar_t.
 //
 // Compute-bound: 4 * (ctx + (i + 1)) * D flop per (query token, head); algorithmic bytes = q + out + the KV it reads.
 #include <float.h>
@@ -44,6 +48,7 @@ struct PrefillParams {
   int64_t q_st, q_sh, k_st, k_sh, v_st, v_sh, o_st, o_sh, kc_sb, kc_sh, vc_sb, vc_sh, bloc_stride;
   int num_heads, num_kv_heads, block_size, bs_shift, sliding_window;
   float scale;
+  float kv_scale;  // fp8 cache: value = float(fp8) * kv_scale
 };
 
 template <typename scalar_t>
@@ -125,17 +130,22 @@ struct RowCtx {
 // maximum) - in steady state that removes the NT x 4 accumulator multiplies of every tile.
 // `fast` (wave-uniform): no alibi, no window, every key of the tile visible to every row - no masks at all, the scale
 // folded into one fma per logit: exp2(s * scale * log2e - m * log2e).
-template <typename scalar_t, int NT>
+// F8 (fp8 cache): K and V of a cached tile are the cache's fp8 values converted at unit scale, and `ks` (wave-uniform:
+// kv_scale on cached tiles, 1 on new-token tiles) restores them in fp32 - folded into the logit scale, and multiplied
+// into the probabilities that feed P.V; the denominator l sums the unscaled probabilities.
+template <typename scalar_t, int NT, bool F8>
 __device__ __forceinline__ void softmax_pv(f32x4 (&s)[2], float& m_run, float& l_part, f32x4 (&o)[NT], const u32x4 (&vf)[NT],
-                                           const RowCtx& rc, float slope_h, int kpos0, int limit, bool causal, bool fast) {
+                                           const RowCtx& rc, float slope_h, int kpos0, int limit, bool causal, bool fast,
+                                           float ks) {
   constexpr float LOG2E = 1.4426950408889634f;
+  const float sc = F8 ? rc.scale * ks : rc.scale;
   // The accumulators o are touched in exactly one place each (the rescale and the MFMAs below), outside the
   // fast / general split: with o written on several control-flow paths hipcc shuffled all NT x 4 of them through
   // copies around every tile.
   float m_tile;
   if (fast) {
     const float mx = max2(max3(max3(s[0][0], s[0][1], s[0][2]), s[0][3], s[1][0]), max3(s[1][1], s[1][2], s[1][3]));
-    m_tile = rows_max(mx) * rc.scale;
+    m_tile = rows_max(mx) * sc;
   } else {
     // a masked logit becomes NEG_BIG: exp2 of it is exactly 0 against any finite running maximum (a row with no
     // visible key yet - only rows past the sequence - gets finite garbage that is never stored)
@@ -145,7 +155,7 @@ __device__ __forceinline__ void softmax_pv(f32x4 (&s)[2], float& m_run, float& l
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int kpos = kpos0 + 16 * u + 4 * rc.g + r;
-        float val = s[u][r] * rc.scale;
+        float val = s[u][r] * sc;
         if (rc.W > 0 && rc.qpos - kpos >= rc.W) val = -10000.f;  // prefix_prefill.py:88-104, :201-204
         if (rc.has_alibi) val += slope_h * (float)(kpos - rc.qpos);  // :552-557
         const bool masked = kpos >= limit || (causal && kpos > rc.qpos) || !rc.row_ok;
@@ -166,7 +176,7 @@ __device__ __forceinline__ void softmax_pv(f32x4 (&s)[2], float& m_run, float& l
   }
   float e[2][4];
   // fast: s is the raw logit, exp2(s * scale * log2e - m * log2e); general: s already scaled / biased, c = log2e
-  const float c = (fast ? rc.scale : 1.f) * LOG2E, mc = -m_run * LOG2E;
+  const float c = (fast ? sc : 1.f) * LOG2E, mc = -m_run * LOG2E;
 #pragma unroll
   for (int u = 0; u < 2; ++u)
 #pragma unroll
@@ -175,8 +185,13 @@ __device__ __forceinline__ void softmax_pv(f32x4 (&s)[2], float& m_run, float& l
 #pragma unroll
   for (int u = 0; u < 2; ++u) {
     l_part += (e[u][0] + e[u][1]) + (e[u][2] + e[u][3]);
-    pk[u][0] = pack2<scalar_t>(e[u][0], e[u][1]);
-    pk[u][1] = pack2<scalar_t>(e[u][2], e[u][3]);
+    if constexpr (F8) {
+      pk[u][0] = pack2<scalar_t>(e[u][0] * ks, e[u][1] * ks);
+      pk[u][1] = pack2<scalar_t>(e[u][2] * ks, e[u][3] * ks);
+    } else {
+      pk[u][0] = pack2<scalar_t>(e[u][0], e[u][1]);
+      pk[u][1] = pack2<scalar_t>(e[u][2], e[u][3]);
+    }
   }
   const u32x4 pb = p_to_operand(pk[0], pk[1]);
 #pragma unroll
@@ -186,8 +201,10 @@ __device__ __forceinline__ void softmax_pv(f32x4 (&s)[2], float& m_run, float& l
 
 // GQ = query heads of one kv head processed by a wave (1 or 2): the K / V fragments of a tile are loaded once and
 // feed GQ x as many MFMAs - the kernel is bound by the wave-instruction rate of its operand loads, not by the MFMAs.
-template <typename scalar_t, int D, int GQ>
+// KV = storage of the cached context: NMX_KV_AUTO (scalar_t, x = 8) or one of the fp8 kinds (one byte per element, x = 16).
+template <typename scalar_t, int D, int GQ, int KV>
 __global__ __launch_bounds__(256) void prefill_attention_kernel(const PrefillParams p) {
+  constexpr bool F8 = KV != NMX_KV_AUTO;
   constexpr int KS = (D + 31) / 32;
   constexpr int NT = D / 16;
   constexpr int CHUNKS = D / 8;
@@ -242,9 +259,9 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const PrefillPar
   const RowCtx rc{qpos, g, W, row_ok, has_alibi, p.scale};
   // one 32-token tile of head h (softmax_pv above); the fast path needs every row valid and every key visible
   const bool plain = !has_alibi && W == 0 && r0 + 16 <= q_len;
-  auto tile_pv = [&](auto hc, f32x4 (&s)[2], int kpos0, int limit, bool causal, const u32x4 (&vf)[NT], bool fast) {
+  auto tile_pv = [&](auto hc, f32x4 (&s)[2], int kpos0, int limit, bool causal, const u32x4 (&vf)[NT], bool fast, float ks) {
     constexpr int h = decltype(hc)::value;
-    softmax_pv<scalar_t, NT>(s, m_runs[h], l_parts[h], os[h], vf, rc, slope[h], kpos0, limit, causal, fast);
+    softmax_pv<scalar_t, NT, F8>(s, m_runs[h], l_parts[h], os[h], vf, rc, slope[h], kpos0, limit, causal, fast, ks);
   };
 
   // Both phases request the next tile's K fragments (and, for the new tokens, the next V tile) before the MFMAs and
@@ -252,7 +269,76 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const PrefillPar
   // or V -> LDS -> transposed read) followed by ~16 MFMAs, and the kernel ran at the latency, not the MFMA, rate.
 
   // ---- phase 1: the cached context (no causal mask: every context token precedes every query token) ----
-  {
+  if constexpr (F8) {
+    // fp8 cache, K [NB, Hkv, D/16, BS, 16] and V [NB, Hkv, D, BS] in bytes. The fragments are the same as below at half
+    // the bytes: lane (g, li) takes, per ks, the 8 bytes of key li that hold d = 8 (4 ks + g) .. + 7 - half g & 1 of
+    // 16-byte chunk 2 ks + (g >> 1) - and, per nt, the 8 bytes of tokens 8 g .. 8 g + 7 of row 16 nt + li. Both stay
+    // raw in registers until they are used (the next tile's K bytes wait through the softmax in half the registers)
+    // and are converted at unit scale; kv_scale enters in softmax_pv.
+    const int32_t* bt = p.b_loc + (int64_t)b * p.bloc_stride;
+    const uint8_t* kc = reinterpret_cast<const uint8_t*>(p.k_cache) + (int64_t)kvh * p.kc_sh;
+    const uint8_t* vc = reinterpret_cast<const uint8_t*>(p.v_cache) + (int64_t)kvh * p.vc_sh;
+    const int BS = p.block_size, last = ctx - 1;
+    auto load_k = [&](int t0, u32x2 (&kq)[2][KS], int64_t& vphys) {
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        const int tok = min(t0 + 16 * u + li, last);
+        const uint8_t* kb = kc + (int64_t)bt[tok >> p.bs_shift] * p.kc_sb + (tok & (BS - 1)) * 16 + (g & 1) * 8;
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) {
+          const int chunk16 = 2 * ks + (g >> 1);
+          u32x2 val = {0, 0};  // fp8 zero in both formats
+          if (chunk16 < D / 16) val = *reinterpret_cast<const u32x2*>(kb + (int64_t)chunk16 * BS * 16);
+          kq[u][ks] = val;
+        }
+      }
+      vphys = bt[min(t0 + 8 * g, last & ~7) >> p.bs_shift];
+    };
+    u32x2 kq[2][KS];
+    int64_t vphys = 0;
+    if (ctx > 0) load_k(0, kq, vphys);
+    for (int t0 = 0; t0 < ctx; t0 += 32) {
+      const bool more = t0 + 32 < ctx;
+      u32x2 vq[NT];
+      const int tokv = t0 + 8 * g;
+      {
+        const int tokc = min(tokv, last & ~7);
+        const uint8_t* vb = vc + vphys * p.vc_sb + (tokc & (BS - 1));
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) vq[nt] = *reinterpret_cast<const u32x2*>(vb + (int64_t)(16 * nt + li) * BS);
+      }
+      f32x4 s[GQ][2];
+#pragma unroll
+      for (int u = 0; u < 2; ++u) {
+        u32x4 kf[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ++ks) kf[ks] = cvt8_fp8_exact<scalar_t, KV>(kq[u][ks]);
+#pragma unroll
+        for (int h = 0; h < GQ; ++h) {
+          s[h][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+          for (int ks = 0; ks < KS; ++ks) s[h][u] = mfma<scalar_t>(kf[ks], qf[h][ks], s[h][u]);
+        }
+      }
+      if (more) load_k(t0 + 32, kq, vphys);  // into the registers the conversions above have just consumed
+      u32x4 vf[NT];
+      {
+        const int nvalid = max(0, min(8, ctx - tokv));  // slots past the context may hold anything (fp8 NaNs included):
+        const uint32_t keep[2] = {                      // blanked on the bytes, token j of the lane in byte j
+            nvalid >= 4 ? 0xffffffffu : ((1u << (8 * nvalid)) - 1u),
+            nvalid >= 8 ? 0xffffffffu : (nvalid > 4 ? (1u << (8 * (nvalid - 4))) - 1u : 0u)};
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) {
+          u32x2 w = vq[nt];
+          if (t0 + 32 > ctx) w = u32x2{w[0] & keep[0], w[1] & keep[1]};
+          vf[nt] = cvt8_fp8_exact<scalar_t, KV>(w);
+        }
+      }
+      const bool fast = plain && t0 + 32 <= ctx;
+      tile_pv(std::integral_constant<int, 0>{}, s[0], t0, ctx, false, vf, fast, p.kv_scale);
+      if constexpr (GQ > 1) tile_pv(std::integral_constant<int, GQ - 1>{}, s[GQ - 1], t0, ctx, false, vf, fast, p.kv_scale);
+    }
+  } else {
     const int32_t* bt = p.b_loc + (int64_t)b * p.bloc_stride;
     const scalar_t* kc = reinterpret_cast<const scalar_t*>(p.k_cache) + (int64_t)kvh * p.kc_sh;
     const scalar_t* vc = reinterpret_cast<const scalar_t*>(p.v_cache) + (int64_t)kvh * p.vc_sh;
@@ -306,8 +392,8 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const PrefillPar
         }
       if (more) load_k(t0 + 32, kf, vphys);  // into the registers the MFMAs above have just consumed
       const bool fast = plain && t0 + 32 <= ctx;
-      tile_pv(std::integral_constant<int, 0>{}, s[0], t0, ctx, false, vf, fast);
-      if constexpr (GQ > 1) tile_pv(std::integral_constant<int, GQ - 1>{}, s[GQ - 1], t0, ctx, false, vf, fast);
+      tile_pv(std::integral_constant<int, 0>{}, s[0], t0, ctx, false, vf, fast, 1.f);
+      if constexpr (GQ > 1) tile_pv(std::integral_constant<int, GQ - 1>{}, s[GQ - 1], t0, ctx, false, vf, fast, 1.f);
     }
   }
 
@@ -378,8 +464,8 @@ __global__ __launch_bounds__(256) void prefill_attention_kernel(const PrefillPar
         }
       }
       const bool fast = plain && t0 + 31 <= r0;
-      tile_pv(std::integral_constant<int, 0>{}, s[0], ctx + t0, ctx + q_len, true, vf, fast);
-      if constexpr (GQ > 1) tile_pv(std::integral_constant<int, GQ - 1>{}, s[GQ - 1], ctx + t0, ctx + q_len, true, vf, fast);
+      tile_pv(std::integral_constant<int, 0>{}, s[0], ctx + t0, ctx + q_len, true, vf, fast, 1.f);
+      if constexpr (GQ > 1) tile_pv(std::integral_constant<int, GQ - 1>{}, s[GQ - 1], ctx + t0, ctx + q_len, true, vf, fast, 1.f);
       __builtin_amdgcn_wave_barrier();
     }
   }
@@ -418,9 +504,20 @@ __device__ __forceinline__ void static_for(F&& f) {
 // buffer after them; one workgroup barrier per tile. Per 32-token tile a wave now issues 2 x D/64 global loads instead
 // of 2 x D/8 (the per-wave kernel above is bound by exactly that instruction stream), and GQ can grow to 4 because the
 // prefetch registers are gone. Context tiles and new-token tiles form one tile sequence.
-template <typename scalar_t, int D, int GQ>
+//
+// fp8 cache (KV != NMX_KV_AUTO; K [NB, Hkv, D/16, BS, 16], V [NB, Hkv, D, BS] in bytes): only the way a cached tile comes
+// in changes. A K tile is 32 x D/16 pieces of 16 bytes (16 consecutive d of one key: 2 D pieces, so at D = 64 half the
+// threads hold none and at D = 192 half hold a second one), a V tile D x 4 pieces of 8 bytes (8 tokens of one d row,
+// never across a block). The bytes wait raw in registers (kr, vq) and store_tile converts them at unit scale
+// into the SAME LDS images - a K piece becomes two adjacent 16-byte chunks of its key's row, a V piece exactly one slot
+// of the fragment image - once per workgroup and tile; compute() reads them as before and kv_scale enters in softmax_pv.
+template <typename scalar_t, int D, int GQ, int KV>
 __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const PrefillParams p) {
   static_assert(D % 64 == 0, "tile pieces must divide evenly over 256 threads");
+  constexpr bool F8 = KV != NMX_KV_AUTO;
+  using cache_t = std::conditional_t<F8, uint8_t, scalar_t>;
+  constexpr int NPK = F8 ? 2 * D : 4 * D;    // K pieces of a cached tile; thread tid holds pieces it * 256 + tid < NPK
+  constexpr int PPK = (NPK + 255) / 256;     // ... so it < PPK; NPK is a multiple of 128
   constexpr int KS = D / 32;
   constexpr int NT = D / 16;
   constexpr int CHUNKS = D / 8;
@@ -479,8 +576,8 @@ __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const Pre
   }
 
   const int32_t* bt = p.b_loc + (int64_t)b * p.bloc_stride;
-  const scalar_t* kc = reinterpret_cast<const scalar_t*>(p.k_cache) + (int64_t)kvh * p.kc_sh;
-  const scalar_t* vc = reinterpret_cast<const scalar_t*>(p.v_cache) + (int64_t)kvh * p.vc_sh;
+  const cache_t* kc = reinterpret_cast<const cache_t*>(p.k_cache) + (int64_t)kvh * p.kc_sh;
+  const cache_t* vc = reinterpret_cast<const cache_t*>(p.v_cache) + (int64_t)kvh * p.vc_sh;
   const int BS = p.block_size, last = ctx - 1;
   const int n1 = (ctx + 31) >> 5;                           // context tiles
   const int n2 = (min(q_len, wg_r0 + 64) + 31) >> 5;        // new-token tiles any wave of this workgroup needs
@@ -510,7 +607,7 @@ __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const Pre
     // cached K piece (key = piece % 32, chunk = piece / 32): neighbouring lanes read neighbouring block offsets; same
     // row-major image as the new tokens' K
     const int key = piece & 31, chunk = piece >> 5;
-    ck_lds[it] = key * KROW + chunk * 16;
+    ck_lds[it] = key * KROW + chunk * (F8 ? 32 : 16);  // fp8: chunk = 16 d, written as two 16-byte halves
     // cached V piece (token group gg = piece % 4, d = piece / 4); image: fragment nt is 1 KiB, row i = d % 16 holds
     // its four groups in slots 4 i + (gg ^ ((i >> 2) & 2)): eight neighbouring lanes write 128 contiguous bytes and
     // every 16-lane group of the fragment read lands on 16 different slots
@@ -532,20 +629,31 @@ __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const Pre
       }
     }
   };
-  auto load_tile = [&](int t, u32x4 (&kr)[PP], u32x4 (&vr)[PP], const int (&kphys)[PP], const int (&vphys)[PP]) {
+  // fp8 cache: the raw bytes of a cached tile have registers of their own (kq, vq), every load fills one whole tuple,
+  // and a thread without a K piece repeats the load of the piece 128 below instead of branching round it. Sharing
+  // kr / vr with the new-token tiles, writing part of a tuple or loading under a condition each cost register copies
+  // where the two kinds of tile meet, and those copies wait for the load right here (measured: 1.46 x the time of the
+  // 16-bit form on 4 x (256 new + 4096 cached)).
+  auto load_tile = [&](int t, u32x4 (&kr)[PP], u32x4 (&vr)[PP], u32x4 (&kq)[PPK], u32x2 (&vq)[PP], const int (&kphys)[PP],
+                       const int (&vphys)[PP]) {
     if (t < n1) {
       const int t0 = t * 32;
 #pragma unroll
       for (int it = 0; it < PP; ++it) {
         const int piece = it * 256 + tid;
-        const int key = piece & 31, chunk = piece >> 5;
+        const int key = piece & 31, chunk = (piece < NPK ? piece : piece - 128) >> 5;
         const int tok = min(t0 + key, last);
-        const scalar_t* kb = kc + (int64_t)kphys[it] * p.kc_sb;
-        kr[it] = *reinterpret_cast<const u32x4*>(kb + ((int64_t)chunk * BS + (tok & (BS - 1))) * 8);
+        const cache_t* kb = kc + (int64_t)kphys[it] * p.kc_sb;
         const int gg = piece & 3, d = piece >> 2;
         const int tokc = min(t0 + 8 * gg, last & ~7);
-        const scalar_t* vb = vc + (int64_t)vphys[it] * p.vc_sb + (tokc & (BS - 1));
-        vr[it] = *reinterpret_cast<const u32x4*>(vb + (int64_t)d * BS);
+        const cache_t* vb = vc + (int64_t)vphys[it] * p.vc_sb + (tokc & (BS - 1));
+        if constexpr (F8) {
+          if (it < PPK) kq[it] = *reinterpret_cast<const u32x4*>(kb + ((int64_t)chunk * BS + (tok & (BS - 1))) * 16);
+          vq[it] = *reinterpret_cast<const u32x2*>(vb + (int64_t)d * BS);
+        } else {
+          kr[it] = *reinterpret_cast<const u32x4*>(kb + ((int64_t)chunk * BS + (tok & (BS - 1))) * 8);
+          vr[it] = *reinterpret_cast<const u32x4*>(vb + (int64_t)d * BS);
+        }
       }
     } else {
       const int adv = t - n1;
@@ -556,10 +664,29 @@ __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const Pre
       }
     }
   };
-  auto store_tile = [&](int t, char* buf, const u32x4 (&kr)[PP], const u32x4 (&vr)[PP]) {
+  auto store_tile = [&](int t, char* buf, const u32x4 (&kr)[PP], const u32x4 (&vr)[PP], const u32x4 (&kq)[PPK],
+                        const u32x2 (&vq)[PP]) {
 #pragma unroll
     for (int it = 0; it < PP; ++it) {
-      if (t < n1) {
+      if constexpr (F8) {
+        if (t >= n1) {
+          *reinterpret_cast<u32x4*>(buf + nv_lds[it]) = vr[it];
+          *reinterpret_cast<u32x4*>(buf + nk_lds[it]) = kr[it];
+          continue;
+        }
+        u32x2 w = vq[it];
+        const int t0 = t * 32;
+        if (t0 + 32 > ctx) {  // slots past the context, blanked on the bytes (token j of the piece in byte j)
+          const int nvalid = max(0, min(8, ctx - (t0 + 8 * (tid & 3))));
+          w[0] &= nvalid >= 4 ? 0xffffffffu : ((1u << (8 * nvalid)) - 1u);
+          w[1] &= nvalid >= 8 ? 0xffffffffu : (nvalid > 4 ? (1u << (8 * (nvalid - 4))) - 1u : 0u);
+        }
+        *reinterpret_cast<u32x4*>(buf + cv_lds[it]) = cvt8_fp8_exact<scalar_t, KV>(w);
+        if (it < PPK && it * 256 + tid < NPK) {
+          *reinterpret_cast<u32x4*>(buf + ck_lds[it]) = cvt8_fp8_exact<scalar_t, KV>(u32x2{kq[it][0], kq[it][1]});
+          *reinterpret_cast<u32x4*>(buf + ck_lds[it] + 16) = cvt8_fp8_exact<scalar_t, KV>(u32x2{kq[it][2], kq[it][3]});
+        }
+      } else if (t < n1) {
         u32x4 val = vr[it];
         const int t0 = t * 32;
         if (t0 + 32 > ctx) {  // slots past the context may hold anything (NaNs included)
@@ -620,29 +747,36 @@ __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const Pre
     const bool fast = plain && (is_ctx ? t0 + 32 <= ctx : t0 + 31 <= r0);
     static_for<0, GQ>([&](auto hc) {
       constexpr int h = decltype(hc)::value;
-      softmax_pv<scalar_t, NT>(s[h], m_runs[h], l_parts[h], os[h], vf, rc, slope[h], kpos0, limit, !is_ctx, fast);
+      softmax_pv<scalar_t, NT, F8>(s[h], m_runs[h], l_parts[h], os[h], vf, rc, slope[h], kpos0, limit, !is_ctx, fast,
+                                   is_ctx ? p.kv_scale : 1.f);
     });
   };
 
   const int nt_all = n1 + n2;
   u32x4 kr[PP], vr[PP];
+  u32x4 kq[PPK];  // fp8 cache: the raw bytes of a cached tile's K and V pieces
+  u32x2 vq[PP];
   int kphys[PP] = {}, vphys[PP] = {};
   load_bt(0, kphys, vphys);
-  load_tile(0, kr, vr, kphys, vphys);
+  load_tile(0, kr, vr, kq, vq, kphys, vphys);
   load_bt(1, kphys, vphys);
-  store_tile(0, smem, kr, vr);
+  store_tile(0, smem, kr, vr, kq, vq);
   __syncthreads();
+  // fp8 form: hipcc sinks the second head's Q loads below the loads of tile 0, nothing up to here waits for them, and
+  // the wait it then places in front of the first MFMAs of the loop body (vmcnt(0), in every iteration) also waits for
+  // the next tile's loads issued just above it. Drain the prologue's loads once, here: s_waitcnt vmcnt(0) on gfx9.
+  if constexpr (F8) __builtin_amdgcn_s_waitcnt(0x0f70);
   for (int t = 0; t < nt_all; ++t) {
     char* buf = smem + (t & 1) * BUF;
     const bool more = t + 1 < nt_all;
     if (more) {
-      load_tile(t + 1, kr, vr, kphys, vphys);
+      load_tile(t + 1, kr, vr, kq, vq, kphys, vphys);
       load_bt(t + 2, kphys, vphys);
     }
     const bool is_ctx = t < n1;
     const int t0 = is_ctx ? t * 32 : (t - n1) * 32;
     if (wave_on && (is_ctx || t0 < n_end)) compute(is_ctx, buf, t0);
-    if (more) store_tile(t + 1, smem + ((t + 1) & 1) * BUF, kr, vr);
+    if (more) store_tile(t + 1, smem + ((t + 1) & 1) * BUF, kr, vr, kq, vq);
     __syncthreads();
   }
 
@@ -663,10 +797,10 @@ __global__ __launch_bounds__(256) void prefill_attention_shared_kernel(const Pre
   }
 }
 
-template <typename scalar_t, int D, int GQ>
+template <typename scalar_t, int D, int GQ, int KV>
 int launch_shared(const PrefillParams& p, int batch, int max_input_len, hipStream_t stream) {
   constexpr int smem = 2 * (32 * (D * 2 + 32) + 32 * (D * 2 + 16));
-  auto kern = prefill_attention_shared_kernel<scalar_t, D, GQ>;
+  auto kern = prefill_attention_shared_kernel<scalar_t, D, GQ, KV>;
   if (smem > 64 * 1024)
     NMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, smem));
   dim3 grid(p.num_heads / GQ, batch, ceil_div(max_input_len, 64));
@@ -675,7 +809,7 @@ int launch_shared(const PrefillParams& p, int batch, int max_input_len, hipStrea
   return NMX_OK;
 }
 
-template <typename scalar_t, int D>
+template <typename scalar_t, int D, int KV>
 int launch(const PrefillParams& p, int batch, int max_input_len, hipStream_t stream) {
   // NMX_PREFILL_GQ: 1 / 2 = the per-wave kernel with that many heads per wave (tests / sweeps); 11 / 12 / 14 = the
   // workgroup-shared kernel with 1 / 2 / 4 heads per wave
@@ -690,9 +824,9 @@ int launch(const PrefillParams& p, int batch, int max_input_len, hipStream_t str
     else if (force == 0 && max_input_len >= 64 && fits32) sgq = (D <= 128 && group % 2 == 0) ? 2 : 1;
     if (sgq == 4 && (D > 128 || group % 4 != 0)) sgq = 2;
     if (sgq == 2 && (D > 128 || group % 2 != 0)) sgq = 1;
-    if (sgq == 4) { if constexpr (D <= 128) return launch_shared<scalar_t, D, 4>(p, batch, max_input_len, stream); }
-    if (sgq == 2) { if constexpr (D <= 128) return launch_shared<scalar_t, D, 2>(p, batch, max_input_len, stream); }
-    if (sgq == 1) return launch_shared<scalar_t, D, 1>(p, batch, max_input_len, stream);
+    if (sgq == 4) { if constexpr (D <= 128) return launch_shared<scalar_t, D, 4, KV>(p, batch, max_input_len, stream); }
+    if (sgq == 2) { if constexpr (D <= 128) return launch_shared<scalar_t, D, 2, KV>(p, batch, max_input_len, stream); }
+    if (sgq == 1) return launch_shared<scalar_t, D, 1, KV>(p, batch, max_input_len, stream);
   }
 
   const size_t smem = (size_t)4 * 32 * (D * 2 + 16);
@@ -704,11 +838,11 @@ int launch(const PrefillParams& p, int batch, int max_input_len, hipStream_t str
   dim3 grid(gq2 ? p.num_heads / 2 : p.num_heads, batch, ceil_div(max_input_len, 64));
   if (gq2) {
     if constexpr (D <= 128) {
-      auto kern = prefill_attention_kernel<scalar_t, D, 2>;
+      auto kern = prefill_attention_kernel<scalar_t, D, 2, KV>;
       kern<<<grid, 256, smem, stream>>>(p);
     }
   } else {
-    auto kern = prefill_attention_kernel<scalar_t, D, 1>;
+    auto kern = prefill_attention_kernel<scalar_t, D, 1, KV>;
     if (smem > 64 * 1024)
       NMX_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
     kern<<<grid, 256, smem, stream>>>(p);
@@ -717,32 +851,45 @@ int launch(const PrefillParams& p, int batch, int max_input_len, hipStream_t str
   return NMX_OK;
 }
 
-template <typename scalar_t>
+template <typename scalar_t, int KV>
 int dispatch_head(const PrefillParams& p, int head_size, int batch, int max_input_len, hipStream_t stream) {
   switch (head_size) {
-    case 64: return launch<scalar_t, 64>(p, batch, max_input_len, stream);
-    case 80: return launch<scalar_t, 80>(p, batch, max_input_len, stream);
-    case 96: return launch<scalar_t, 96>(p, batch, max_input_len, stream);
-    case 112: return launch<scalar_t, 112>(p, batch, max_input_len, stream);
-    case 128: return launch<scalar_t, 128>(p, batch, max_input_len, stream);
-    case 192: return launch<scalar_t, 192>(p, batch, max_input_len, stream);
-    case 256: return launch<scalar_t, 256>(p, batch, max_input_len, stream);
+    case 64: return launch<scalar_t, 64, KV>(p, batch, max_input_len, stream);
+    case 80: return launch<scalar_t, 80, KV>(p, batch, max_input_len, stream);
+    case 96: return launch<scalar_t, 96, KV>(p, batch, max_input_len, stream);
+    case 112: return launch<scalar_t, 112, KV>(p, batch, max_input_len, stream);
+    case 128: return launch<scalar_t, 128, KV>(p, batch, max_input_len, stream);
+    case 192: return launch<scalar_t, 192, KV>(p, batch, max_input_len, stream);
+    case 256: return launch<scalar_t, 256, KV>(p, batch, max_input_len, stream);
     default: NMX_CHECK(false, NMX_ERR_UNSUPPORTED, "context_attention_fwd: unsupported head size %d", head_size);
   }
 }
 
 }  // namespace
 
-extern "C" int nmx_context_attention_fwd(void* out, const void* q, const void* k, const void* v, const void* k_cache,
-                                         const void* v_cache, const int32_t* b_loc, const int32_t* b_start_loc,
-                                         const int32_t* b_seq_len, const int32_t* b_ctx_len, const float* alibi_slopes,
-                                         int batch, int num_heads, int num_kv_heads, int head_size, int block_size, int x,
-                                         int64_t q_st, int64_t q_sh, int64_t k_st, int64_t k_sh, int64_t v_st,
-                                         int64_t v_sh, int64_t o_st, int64_t o_sh, int64_t kc_sb, int64_t kc_sh,
-                                         int64_t vc_sb, int64_t vc_sh, int64_t bloc_stride, int max_input_len,
-                                         int sliding_window, float sm_scale, int dtype, nmx_stream_t stream) {
+extern "C" int nmx_context_attention_fwd_kv(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                            const void* v_cache, const int32_t* b_loc, const int32_t* b_start_loc,
+                                            const int32_t* b_seq_len, const int32_t* b_ctx_len, const float* alibi_slopes,
+                                            int batch, int num_heads, int num_kv_heads, int head_size, int block_size, int x,
+                                            int64_t q_st, int64_t q_sh, int64_t k_st, int64_t k_sh, int64_t v_st,
+                                            int64_t v_sh, int64_t o_st, int64_t o_sh, int64_t kc_sb, int64_t kc_sh,
+                                            int64_t vc_sb, int64_t vc_sh, int64_t bloc_stride, int max_input_len,
+                                            int sliding_window, float sm_scale, int dtype, int kv_dtype, float kv_scale,
+                                            nmx_stream_t stream) {
   NMX_CHECK(dtype == NMX_F16 || dtype == NMX_BF16, NMX_ERR_UNSUPPORTED, "context_attention_fwd: float16 / bfloat16 only");
-  NMX_CHECK(x == 8, NMX_ERR_UNSUPPORTED, "context_attention_fwd: the key cache must use x = 8 (16-bit cache), got %d", x);
+  NMX_CHECK(kv_dtype == NMX_KV_AUTO || kv_dtype == NMX_KV_FP8_E4M3 || kv_dtype == NMX_KV_FP8_E5M2, NMX_ERR_UNSUPPORTED,
+            "context_attention_fwd: unsupported kv cache dtype %d", kv_dtype);
+  const bool f8 = kv_dtype != NMX_KV_AUTO;
+  if (f8) {  // cache strides are in elements = bytes: 16-byte K pieces, 8-byte V pieces
+    NMX_CHECK(x == 16, NMX_ERR_UNSUPPORTED, "context_attention_fwd: an fp8 key cache must use x = 16, got %d", x);
+    NMX_CHECK(kv_scale > 0.f, NMX_ERR_INVALID_ARG, "context_attention_fwd: kv_scale must be positive, got %g", (double)kv_scale);
+    NMX_CHECK(kc_sb % 16 == 0 && kc_sh % 16 == 0 && (uintptr_t)k_cache % 16 == 0 && vc_sb % 8 == 0 && vc_sh % 8 == 0 &&
+                  (uintptr_t)v_cache % 8 == 0,
+              NMX_ERR_INVALID_ARG,
+              "context_attention_fwd: an fp8 cache must be aligned to 16 bytes (keys) / 8 bytes (values), strides included");
+  } else {
+    NMX_CHECK(x == 8, NMX_ERR_UNSUPPORTED, "context_attention_fwd: the key cache must use x = 8 (16-bit cache), got %d", x);
+  }
   NMX_CHECK(block_size == 8 || block_size == 16 || block_size == 32, NMX_ERR_UNSUPPORTED, "Unsupported block size: %d",
             block_size);
   NMX_CHECK(num_kv_heads > 0 && num_heads % num_kv_heads == 0, NMX_ERR_INVALID_ARG,
@@ -750,7 +897,7 @@ extern "C" int nmx_context_attention_fwd(void* out, const void* q, const void* k
   NMX_CHECK(q_st % 8 == 0 && q_sh % 8 == 0 && k_st % 8 == 0 && k_sh % 8 == 0 && v_st % 8 == 0 && v_sh % 8 == 0 &&
                 o_st % 4 == 0 && o_sh % 4 == 0 && kc_sb % 8 == 0 && kc_sh % 8 == 0 && vc_sb % 8 == 0 && vc_sh % 8 == 0 &&
                 (uintptr_t)q % 16 == 0 && (uintptr_t)k % 16 == 0 && (uintptr_t)v % 16 == 0 && (uintptr_t)out % 8 == 0 &&
-                (uintptr_t)k_cache % 16 == 0 && (uintptr_t)v_cache % 16 == 0,
+                (uintptr_t)k_cache % 16 == 0 && (uintptr_t)v_cache % (f8 ? 8 : 16) == 0,
             NMX_ERR_INVALID_ARG, "context_attention_fwd: tensors must be 16-byte aligned with strides in multiples of 8");
   if (batch == 0 || max_input_len <= 0) return NMX_OK;
   NMX_CHECK(batch <= 65535, NMX_ERR_UNSUPPORTED, "context_attention_fwd: at most 65535 sequences per call, got %d", batch);
@@ -764,6 +911,28 @@ extern "C" int nmx_context_attention_fwd(void* out, const void* q, const void* k
   p.bs_shift = block_size == 8 ? 3 : (block_size == 16 ? 4 : 5);
   p.sliding_window = sliding_window > 0 ? sliding_window : 0;
   p.scale = sm_scale;
-  if (dtype == NMX_F16) return dispatch_head<f16>(p, head_size, batch, max_input_len, (hipStream_t)stream);
-  return dispatch_head<bf16>(p, head_size, batch, max_input_len, (hipStream_t)stream);
+  p.kv_scale = f8 ? kv_scale : 1.f;
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == NMX_F16) {
+    if (kv_dtype == NMX_KV_FP8_E4M3) return dispatch_head<f16, NMX_KV_FP8_E4M3>(p, head_size, batch, max_input_len, st);
+    if (kv_dtype == NMX_KV_FP8_E5M2) return dispatch_head<f16, NMX_KV_FP8_E5M2>(p, head_size, batch, max_input_len, st);
+    return dispatch_head<f16, NMX_KV_AUTO>(p, head_size, batch, max_input_len, st);
+  }
+  if (kv_dtype == NMX_KV_FP8_E4M3) return dispatch_head<bf16, NMX_KV_FP8_E4M3>(p, head_size, batch, max_input_len, st);
+  if (kv_dtype == NMX_KV_FP8_E5M2) return dispatch_head<bf16, NMX_KV_FP8_E5M2>(p, head_size, batch, max_input_len, st);
+  return dispatch_head<bf16, NMX_KV_AUTO>(p, head_size, batch, max_input_len, st);
+}
+
+extern "C" int nmx_context_attention_fwd(void* out, const void* q, const void* k, const void* v, const void* k_cache,
+                                         const void* v_cache, const int32_t* b_loc, const int32_t* b_start_loc,
+                                         const int32_t* b_seq_len, const int32_t* b_ctx_len, const float* alibi_slopes,
+                                         int batch, int num_heads, int num_kv_heads, int head_size, int block_size, int x,
+                                         int64_t q_st, int64_t q_sh, int64_t k_st, int64_t k_sh, int64_t v_st,
+                                         int64_t v_sh, int64_t o_st, int64_t o_sh, int64_t kc_sb, int64_t kc_sh,
+                                         int64_t vc_sb, int64_t vc_sh, int64_t bloc_stride, int max_input_len,
+                                         int sliding_window, float sm_scale, int dtype, nmx_stream_t stream) {
+  return nmx_context_attention_fwd_kv(out, q, k, v, k_cache, v_cache, b_loc, b_start_loc, b_seq_len, b_ctx_len, alibi_slopes,
+                                      batch, num_heads, num_kv_heads, head_size, block_size, x, q_st, q_sh, k_st, k_sh, v_st,
+                                      v_sh, o_st, o_sh, kc_sb, kc_sh, vc_sb, vc_sh, bloc_stride, max_input_len,
+                                      sliding_window, sm_scale, dtype, NMX_KV_AUTO, 1.f, stream);
 }
