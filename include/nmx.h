@@ -364,6 +364,30 @@ int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_native, const 
                             int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int* splits_out,
                             nmx_stream_t stream);
 
+/* Zero points on the native layout (AWQ): W[k, n] = (q - z[k / 128, n]) * s[k / 128, n]. fp16 only, size_k % 128 ==
+ * 0, size_n % 64 == 0, groups of 128 (num_groups == size_k / 128): nmx_awq_native_supported(). qweight_native and scales_native
+ * are exactly as above; the addition to the contract:
+ *   zeros_native    fp16 [num_groups, size_n], element order [G][c = n / 64][r = 0..15][t = 0..3], element (G, c, r, t) = 1024 + z
+ *     of column n = 64 c + 16 t + r in group G (bits 0x6400 | z): the four zero points a lane needs for a 128-k unit - one per
+ *     tile - are 8 contiguous bytes, the same for its four lane groups g. 1024 + z is what the kernel subtracts from the low
+ *     nibbles' 1024 + q; the high nibbles' addend 64 + z is that value minus 960. Both are exact in fp16, so q - z is exact; the
+ *     fp32 group sums and the scale multiply are those of nmx_w4a16_gemm.
+ * nmx_awq_native_repack: AWQ checkpoint qweight [size_k, size_n / 8] int32, qzeros [num_groups, size_n / 8] int32 (both with
+ * W[k, 8 c + j] in nibble o_j, o = [0,4,1,5,2,6,3,7], as nmx_awq_gemm) + scales [num_groups, size_n] fp16 -> the native triple, one
+ * launch. nmx_w4a16_zp_*: nmx_w4a16_* with zeros_native after scales_native; the same NMX_W4A16 override and split-K slabs.
+ * There is no 128-row form: a forced mt = 8 runs, and nmx_w4a16_zp_gemm_plan reports, mt = 4. All entries only enqueue. */
+int nmx_awq_native_supported(int size_n, int size_k, int num_groups);
+int nmx_awq_native_repack(const int32_t* qweight, const int32_t* qzeros, const void* scales, int32_t* qweight_native,
+                          void* scales_native, void* zeros_native, int size_k, int size_n, int num_groups, nmx_stream_t stream);
+int64_t nmx_w4a16_zp_gemm_scratch_bytes(int size_m, int size_n, int size_k);
+int nmx_w4a16_zp_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits);
+int nmx_w4a16_zp_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, const void* zeros_native, void* c,
+                      void* scratch, int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype,
+                      nmx_stream_t stream);
+int nmx_w4a16_zp_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native, const void* zeros_native,
+                               void* c, void* scratch, int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups,
+                               int dtype, int* splits_out, nmx_stream_t stream);
+
 /* The 8-bit form of the native layout (nmx_w4a16_supported(.., num_bits = 8, ..): the shape rules of 4 bits). Checkpoint qweight
  * [size_k / 4, size_n] int32, code k % 4 of row k / 4 at bits 8 (k % 4); W[k, n] = (q - 128) * s[group(k), n]. The contract:
  *   qweight_native  int32 [size_k / 128, size_n * 32], element order [u = k / 128][c = n / 64][s][h][lane l = 16 g + r][w]:

@@ -1045,7 +1045,8 @@ def awq_marlin_gemm_deferred(a: torch.Tensor, marlin_q: torch.Tensor, marlin_sca
 # ---------------------------------------------------------------------------------------------------------
 # CDNA4-native W4A16 / W8A16 (extension; layout contract in include/nmx.h): GPTQ checkpoint tensors repacked once into the order the
 # gfx950 MFMA consumes, and the GEMM on it. 4- or 8-bit symmetric (num_bits), fp16 / bf16, K % 128 == 0, N % 64 == 0, channel-wise
-# or 128-k groups. num_bits = 8 routes the same ops to the nmx_w8a16_* entries.
+# or 128-k groups. num_bits = 8 routes the same ops to the nmx_w8a16_* entries; zeros_native (awq_native_repack: AWQ, fp16, 128-k
+# groups) routes them to the nmx_w4a16_zp_* entries, W = (q - z) * s.
 # ---------------------------------------------------------------------------------------------------------
 def w4a16_supported(size_n: int, size_k: int, num_groups: int, num_bits: int = 4, has_act_order: bool = False) -> bool:
     return bool(_lib.lib().nmx_w4a16_supported(c_int(size_n), c_int(size_k), c_int(num_groups), c_int(num_bits),
@@ -1076,47 +1077,86 @@ def w4a16_repack(qweight: torch.Tensor, scales: torch.Tensor, num_bits: int = 4)
     return out_q, out_s
 
 
-def _w4a16_call(entry: str, num_bits: int, a, qweight_native, scales_native, size_m, size_n, size_k, *tail):
+def _w4a16_zp(zeros_native, num_bits: int) -> str:
+    """Entry family: "nmx_w4a16_zp_*" with zeros_native (4 bits only), else the symmetric one of num_bits."""
+    if zeros_native is not None and num_bits != 4:
+        raise ValueError(f"w4a16_gemm: zeros_native needs num_bits = 4, got {num_bits}")
+    return "zp_" if zeros_native is not None else ""
+
+
+def _w4a16_call(entry: str, num_bits: int, a, qweight_native, scales_native, size_m, size_n, size_k, *tail, zeros_native=None):
     _dev(a)
-    fn, pack = _w4a16_entry(entry, num_bits), 32 // num_bits
+    zp = _w4a16_zp(zeros_native, num_bits)
+    fn, pack = _w4a16_entry(zp + entry, num_bits), 32 // num_bits
     if a.dim() != 2 or a.shape[0] != size_m or a.shape[1] != size_k or not a.is_contiguous():
         raise RuntimeError(f"w4a16_gemm: a must be a contiguous [size_m = {size_m}, size_k = {size_k}] tensor, got {tuple(a.shape)}")
     if qweight_native.dtype != torch.int32 or qweight_native.numel() * pack != size_k * size_n or not qweight_native.is_contiguous():
         raise RuntimeError(f"w4a16_gemm: qweight_native must hold size_k * size_n / {pack} = {size_k * size_n // pack} int32 words")
     if scales_native.dtype != a.dtype or scales_native.dim() != 2 or scales_native.shape[1] != size_n or not scales_native.is_contiguous():
         raise RuntimeError("w4a16_gemm: scales_native [G, size_n] must have the dtype of a")
+    zeros = ()
+    if zeros_native is not None:
+        if a.dtype != torch.float16 or zeros_native.dtype != torch.float16:
+            raise RuntimeError("w4a16_gemm: zeros_native is served for float16 only")
+        if zeros_native.shape != scales_native.shape or not zeros_native.is_contiguous() or zeros_native.device != a.device:
+            raise RuntimeError(f"w4a16_gemm: zeros_native must be a contiguous [G, size_n] = {tuple(scales_native.shape)} tensor on the device of a")
+        zeros = (_p(zeros_native), )
     c = torch.empty((size_m, size_n), dtype=a.dtype, device=a.device)
-    need = _w4a16_entry("gemm_scratch_bytes", num_bits)(c_int(size_m), c_int(size_n), c_int(size_k))
+    need = _w4a16_entry(zp + "gemm_scratch_bytes", num_bits)(c_int(size_m), c_int(size_n), c_int(size_k))
     scratch = _get_scratch(a.device, int(need))
-    _lib.check(fn(_p(a), _p(qweight_native), _p(scales_native), _p(c), _p(scratch), c_i64(scratch.numel()), c_int(size_m),
+    _lib.check(fn(_p(a), _p(qweight_native), _p(scales_native), *zeros, _p(c), _p(scratch), c_i64(scratch.numel()), c_int(size_m),
                   c_int(size_n), c_int(size_k), c_int(scales_native.shape[0]), c_int(_dt(a)), *tail, _stream(a)))
     return c, scratch
 
 
 def w4a16_gemm(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor, size_m: int, size_n: int,
-               size_k: int, num_bits: int = 4) -> torch.Tensor:
-    return _w4a16_call("gemm", num_bits, a, qweight_native, scales_native, size_m, size_n, size_k)[0]
+               size_k: int, num_bits: int = 4, zeros_native: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """zeros_native (awq_native_repack): W = (q - z) * s instead of (q - 8) * s; fp16, 4 bits, one group per 128 k."""
+    return _w4a16_call("gemm", num_bits, a, qweight_native, scales_native, size_m, size_n, size_k, zeros_native=zeros_native)[0]
 
 
-def w4a16_gemm_plan(size_m: int, size_n: int, size_k: int, num_bits: int = 4):
+def w4a16_gemm_plan(size_m: int, size_n: int, size_k: int, num_bits: int = 4, zeros_native: Optional[torch.Tensor] = None):
     """(mt, nw, splits) that w4a16_gemm launches for this shape under the current NMX_W4A16 override: mt 16-row tiles per
-    workgroup (8 = the tall kernel, 4 bits only), nw waves of the mt = 1 form (4 otherwise), splits K splits across workgroups."""
+    workgroup (8 = the tall kernel, 4 bits without zeros_native only), nw waves of the mt = 1 form (4 otherwise), splits K splits
+    across workgroups."""
     mt, nw, splits = c_int(0), c_int(0), c_int(0)
-    _lib.check(_w4a16_entry("gemm_plan", num_bits)(c_int(size_m), c_int(size_n), c_int(size_k), ctypes.byref(mt), ctypes.byref(nw),
-                                                   ctypes.byref(splits)))
+    _lib.check(_w4a16_entry(_w4a16_zp(zeros_native, num_bits) + "gemm_plan", num_bits)(
+        c_int(size_m), c_int(size_n), c_int(size_k), ctypes.byref(mt), ctypes.byref(nw), ctypes.byref(splits)))
     return mt.value, nw.value, splits.value
 
 
 def w4a16_gemm_deferred(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor, size_m: int, size_n: int,
-                        size_k: int, num_bits: int = 4) -> DeferredGemm:
+                        size_k: int, num_bits: int = 4, zeros_native: Optional[torch.Tensor] = None) -> DeferredGemm:
     """w4a16_gemm whose split-K partial sums are left for the consumer op, like gptq_marlin_gemm_deferred."""
     splits = c_int(1)
     c, scratch = _w4a16_call("gemm_deferred", num_bits, a, qweight_native, scales_native, size_m, size_n, size_k,
-                             ctypes.byref(splits))
+                             ctypes.byref(splits), zeros_native=zeros_native)
     if (splits.value & 0xff) > 1:
         partial, n = _slabs(scratch, splits.value, size_m, size_n)
         return DeferredGemm(c, partial, n)
     return DeferredGemm(c, None, 1)
+
+
+def awq_native_supported(size_n: int, size_k: int, num_groups: int) -> bool:
+    return bool(_lib.lib().nmx_awq_native_supported(c_int(size_n), c_int(size_k), c_int(num_groups)))
+
+
+def awq_native_repack(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch.Tensor):
+    """AWQ checkpoint qweight [K, N / 8] int32, qzeros [K / 128, N / 8] int32, scales [K / 128, N] fp16 -> (qweight_native
+    [K / 128, 16 N] int32, scales_native [G, N] fp16, zeros_native [G, N] fp16) for w4a16_gemm(..., zeros_native=...)."""
+    _dev(qweight)
+    if qweight.dtype != torch.int32 or qzeros.dtype != torch.int32 or qweight.dim() != 2 or scales.dim() != 2:
+        raise RuntimeError("awq_native_repack: qweight [K, N / 8] and qzeros [G, N / 8] int32 and scales [G, N] expected")
+    k, n, groups = qweight.shape[0], qweight.shape[1] * 8, scales.shape[0]
+    if scales.dtype != torch.float16 or scales.shape[1] != n or qzeros.shape != (groups, n // 8):
+        raise RuntimeError("awq_native_repack: scales [G, N] fp16 and qzeros [G, N / 8] expected")
+    if not (qweight.is_contiguous() and qzeros.is_contiguous() and scales.is_contiguous() and qzeros.is_cuda and scales.is_cuda):
+        raise RuntimeError("awq_native_repack: contiguous GPU tensors expected")
+    out_q = torch.empty((k // 128, n * 16), dtype=torch.int32, device=qweight.device)
+    out_s, out_z = torch.empty_like(scales), torch.empty_like(scales)
+    _lib.check(_lib.lib().nmx_awq_native_repack(_p(qweight), _p(qzeros), _p(scales), _p(out_q), _p(out_s), _p(out_z), c_int(k),
+                                                c_int(n), c_int(groups), _stream(qweight)))
+    return out_q, out_s, out_z
 
 
 def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor, b_gptq_qzeros: torch.Tensor, b_gptq_scales: torch.Tensor,

@@ -50,4 +50,34 @@ __device__ __forceinline__ u32x4 w4_fragment(uint32_t w, uint32_t magic) {
   }
 }
 
+// The zero-point form (fp16; include/nmx.h "zeros_native"): 8 values q - z, exact. The two wave-uniform addends
+// of w4_fragment become per-lane ones: zlo = (1024 + z, 1024 + z) is subtracted from the low nibbles' 1024 + q, zhi =
+// (64 + z, 64 + z) from the high nibbles' (1024 + 16 q) / 16. Same 9 VALU per word (the subtractions are source modifiers).
+__device__ __forceinline__ u32x4 w4_fragment_zp(uint32_t w, uint32_t magic, f16x2 zlo, f16x2 zhi) {
+  const f16x2 r16 = __builtin_bit_cast(f16x2, 0x2c002c00u);
+  const uint32_t w8 = w >> 8;
+  const f16x2 p0 = __builtin_bit_cast(f16x2, and_or_w4(w, 0x000f000fu, magic)) - zlo;
+  const f16x2 p1 = __builtin_bit_cast(f16x2, and_or_w4(w, 0x00f000f0u, magic)) * r16 - zhi;
+  const f16x2 p2 = __builtin_bit_cast(f16x2, and_or_w4(w8, 0x000f000fu, magic)) - zlo;
+  const f16x2 p3 = __builtin_bit_cast(f16x2, and_or_w4(w8, 0x00f000f0u, magic)) * r16 - zhi;
+  return u32x4{__builtin_bit_cast(uint32_t, p0), __builtin_bit_cast(uint32_t, p1), __builtin_bit_cast(uint32_t, p2),
+               __builtin_bit_cast(uint32_t, p3)};
+}
+
+// A lane's zero row of one 128-k unit (4 fp16 values 1024 + z, tiles 0..3) -> the packed addends of its four tiles, once per
+// unit: one v_perm_b32 and one v_pk_add_f16 (-960: 1024 + z -> 64 + z, exact) per tile.
+struct W4Zeros {
+  f16x2 lo[4], hi[4];
+};
+__device__ __forceinline__ W4Zeros w4_zero_addends(u32x2 z) {
+  const f16x2 n960 = __builtin_bit_cast(f16x2, 0xe380e380u);
+  W4Zeros o;
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    o.lo[t] = __builtin_bit_cast(f16x2, __builtin_amdgcn_perm(0u, z[t >> 1], (t & 1) ? 0x03020302u : 0x01000100u));
+    o.hi[t] = o.lo[t] + n960;
+  }
+  return o;
+}
+
 }  // namespace

@@ -11,6 +11,8 @@
 //   scales_native   scalar [G][N / 64][g][t][j] = scales[G][64 c + 16 t + 4 g + j]: the 16 scales of a lane's accumulators
 //       (D row 4 g + j of tile t) are 32 contiguous bytes. The scales multiply the fp32 accumulators of a 128-k unit, not the
 //       weights: (q - 8) * s cannot be formed by one fp16 FMA on the magic-number form (the addend -1032 s needs 19 bits).
+//   zeros_native    fp16 [G][N / 64][r][t] = 1024 + z[G][64 c + 16 t + r] (AWQ, fp16, one group per 128 k): the zero points of a
+//       lane's column in its four tiles are 8 contiguous bytes; W[k, n] = (q - z) * s.
 #include "w4a16_fragment.h"
 
 #include <stdlib.h>
@@ -25,6 +27,7 @@ struct W4Params {
   float* partial;         // [k_splits, M, N] fp32 slabs (k_splits > 1)
   int M, N, K, num_groups, k_splits;
   int xcd_per;            // > 0: XCDs per K split (2 / 4 / 8 splits, the split is chosen by the workgroup id % 8)
+  const void* zeros;      // zeros_native (the zero-point form only)
 };
 
 struct W4Cfg { int mt, nw, splits; };
@@ -62,6 +65,46 @@ __global__ void w4a16_repack_kernel(const uint32_t* __restrict__ qweight, const 
   repack_scale(o, scales, snative, N, G);
 }
 
+// ---- repack of an AWQ checkpoint: qweight [K, N / 8] and qzeros [K / 128, N / 8] (W[k, 8 c + j] in nibble O[j], O = [0, 4, 1, 5,
+// 2, 6, 3, 7]) + scales [K / 128, N] fp16 -> the native triple. The checkpoint packs along N, the native word along K: a native
+// word gathers one nibble position of 8 source words down K. A workgroup takes one 128-k unit x 256 columns (4 column groups):
+// its 128 x 32 source words go through LDS - a wave reads two whole 128-byte rows per pass - and every thread then builds 16
+// native words from it (8 LDS reads each, the 16 lanes of a tile pair on 2 words of a row: broadcasts), written as 4 KiB runs.
+// zeros_native [G][N / 64][r][t] = fp16 (1024 + z) of column 64 c + 16 t + r, element o by thread o; scales: repack_scale.
+__global__ __launch_bounds__(256) void awq_native_repack_kernel(const uint32_t* __restrict__ qweight, const uint32_t* __restrict__ qzeros,
+                                                                const uint16_t* __restrict__ scales, uint32_t* __restrict__ qnative,
+                                                                uint16_t* __restrict__ snative, uint16_t* __restrict__ znative, int K, int N) {
+  __shared__ uint32_t tile[128][33];  // (+ 1: the 8 rows of a native word on 8 banks)
+  const int C = N / 64, NW = N / 8, CW = (C + 3) / 4;
+  const int u = blockIdx.x / CW, cw = blockIdx.x % CW;
+  for (int e = threadIdx.x; e < 128 * 32; e += 256) {
+    const int row = e >> 5, w = e & 31;
+    if (32 * cw + w < NW) tile[row][w] = qweight[(int64_t)(128 * u + row) * NW + 32 * cw + w];
+  }
+  __syncthreads();
+  const int ngroups = min(4, C - 4 * cw);
+  for (int e = threadIdx.x; e < ngroups * 1024; e += 256) {  // word (s, l = 16 g + r, t) of column group 4 cw + (e >> 10)
+    const int t = e & 3, l = (e >> 2) & 63, s = (e >> 8) & 3;
+    const int n = 64 * (e >> 10) + 16 * t + (l & 15);  // column inside the tile
+    const int sh = 4 * ((n & 1) * 4 + ((n & 7) >> 1));  // O[n % 8]
+    const int row = 32 * s + 8 * (l >> 4);
+    uint32_t r = 0;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) r |= ((tile[row + j][n >> 3] >> sh) & 0xfu) << (4 * ((j >> 1) + 4 * (j & 1)));
+    qnative[((int64_t)u * C + 4 * cw) * 1024 + e] = r;
+  }
+  const int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x;  // (grid: K / 128 * CW * 256 >= K / 128 * N threads)
+  const int G = K / 128;
+  if (o < (int64_t)G * N) {
+    const int t = (int)(o & 3), r = (int)(o >> 2) & 15;
+    const int64_t gc = o >> 6;
+    const int n = 64 * (int)(gc % C) + 16 * t + r;
+    const uint32_t z = (qzeros[(gc / C) * NW + (n >> 3)] >> (4 * ((n & 1) * 4 + ((n & 7) >> 1)))) & 0xfu;
+    znative[o] = (uint16_t)(0x6400u | z);  // fp16 1024 + z
+  }
+  repack_scale(o, scales, snative, N, G);
+}
+
 // ---- the GEMM. c [M, N] = a [M, K] . W, W[k, n] = (q - 8) * s[group(k), n].
 // D = W^T-tile (A operand, 16 columns x 32 k) x activations (B operand, 32 k x 16 rows): lane (g, r) of tile t holds rows
 // m = r, columns 16 t + 4 g + 0..3 - four consecutive outputs, one 8-byte store.
@@ -75,9 +118,13 @@ __global__ void w4a16_repack_kernel(const uint32_t* __restrict__ qweight, const 
 // (2 x 4 KiB per wave in flight), waits counted by hipcc. GROUPED: one scale row per 128-k unit, applied to the unit's fp32
 // accumulators; channel-wise scales are applied once, in the epilogue. (GROUPED at MT = 4 holds 64 + 64 accumulators: it takes
 // more than the 256 registers of two workgroups per CU, so that one form is compiled for one.)
-template <typename scalar_t, int MT, int NW, bool GROUPED, bool STAGED>
+// ZP (fp16, GROUPED): W[k, n] = (q - z[group(k), n]) * s[group(k), n]. The lane's zero row of a unit (8 bytes of zeros_native: its
+// column's zero point in each of the four tiles) is loaded right after the unit's scale row, in the same ring; compute_unit
+// turns it into the packed addends of w4_fragment_zp before the unit's first step.
+template <typename scalar_t, int MT, int NW, bool GROUPED, bool STAGED, bool ZP = false>
 __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_gemm_kernel(const W4Params p) {
   static_assert(STAGED ? NW == 4 : MT == 1, "staged: 4 waves = 4 column groups; unstaged: one 16-row tile");
+  static_assert(!ZP || (GROUPED && __is_same(scalar_t, f16)), "zero points: fp16, one zero row per 128-k unit");
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int g = lane >> 4, r = lane & 15;
@@ -115,6 +162,8 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_g
   const int unit_bytes = C * 4096;  // one 128-k unit of all column groups
   const int w_voff = cl * 4096 + lane * 16;
   const int s_voff = (cl * 4 + g) * 32;
+  const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.zeros), 0, ZP ? p.num_groups * N * 2 : 0, 0x00020000);
+  const int z_voff = (cl * 16 + r) * 8;
   constexpr int kPast = 0x7ff00000;  // beyond every descriptor: the load returns zeros
   // unstaged: the lane's own row; staged: chunk e = tid + 256 i of the tile image (row e >> 4, 16-byte chunk e & 15)
   int a_voff[STAGED ? MT : 1], a_lds[STAGED ? MT : 1];
@@ -137,6 +186,7 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_g
     u32x4 q[4];
     u32x4 a[STAGED ? 1 : 4];
     u32x4 s[2];
+    u32x2 z;
   };
   // loads of one 32-k step / the scale row of unit u (past the slice: the last unit again, never consumed). sched_barrier pins
   // the issue order: prologue and loop must queue the loads alike, or the merged wait counts at the loop head degrade.
@@ -151,6 +201,7 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_g
       u = min(u, total_units - 1);  // one group per unit
       U.s[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff, u * N * 2, 0);
       U.s[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_s, s_voff + 16, u * N * 2, 0);
+      if constexpr (ZP) U.z = __builtin_amdgcn_raw_buffer_load_b64(rs_z, z_voff, u * N * 2, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -186,6 +237,8 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_g
   // as soon as it is free
   auto compute_unit = [&](Unit& U, int next, const char* buf, bool reissue) {
     f32x4 gacc[GROUPED ? MT : 1][4];
+    W4Zeros zp;
+    if constexpr (ZP) zp = w4_zero_addends(U.z);
 #pragma unroll
     for (int ks = 0; ks < 4; ++ks) {
       u32x4 bf[MT];
@@ -198,7 +251,9 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w4a16_g
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        const u32x4 wf = w4_fragment<scalar_t>(U.q[ks][t], magic);
+        u32x4 wf;
+        if constexpr (ZP) wf = w4_fragment_zp(U.q[ks][t], magic, zp.lo[t], zp.hi[t]);
+        else wf = w4_fragment<scalar_t>(U.q[ks][t], magic);
 #pragma unroll
         for (int mt = 0; mt < MT; ++mt) {
           if constexpr (GROUPED) gacc[mt][t] = mfma_w4<scalar_t>(wf, bf[mt], ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : gacc[mt][t]);
@@ -805,7 +860,8 @@ __global__ __launch_bounds__(64 * NW, (GROUPED && MT == 4) ? 1 : 2) void w8a16_g
 // mt: 16-row tiles per workgroup (1: the unstaged form, 2 / 4: staged, 8: the tall kernel), nw: waves of the unstaged form
 // (4 / 8), splits: K splits across workgroups - only to fill the 256 CUs, and only while every wave keeps >= 2 units (the tall
 // kernel: >= 4). NMX_W4A16 = "mt,nw,splits" forces any of them for sweeps and tests (0 = keep the default).
-W4Cfg w4_pick(int M, int N, int K) {
+// tall = false (the zero-point form has no 128-row kernel): a forced mt = 8 falls to 4, as at 8 bits.
+W4Cfg w4_pick(int M, int N, int K, bool tall = true) {
   W4Cfg c;
   // Measured (tools/lean_sweep.py N: family, Llama-3-8B shapes): the unstaged form wins at M = 1 everywhere and
   // at M = 16 on qkv / o; at M = 16 the big matrices (down, gate_up: >= 24 MiB of weights) take the staged 32-row tile
@@ -820,6 +876,7 @@ W4Cfg w4_pick(int M, int N, int K) {
   int f_mt = 0, f_nw = 0, f_splits = 0;
   if (const char* e = nmx_tune(NMX_TUNE_W4A16)) sscanf(e, "%d,%d,%d", &f_mt, &f_nw, &f_splits);
   if (f_mt == 1 || f_mt == 2 || f_mt == 4 || f_mt == 8) c.mt = f_mt;
+  if (c.mt == 8 && !tall) c.mt = 4;
   if (c.mt == 1 && f_nw == 8) c.nw = 8;
   const int units = K / 128, groups = N / 64;
   const int row_blocks = ceil_div(M, 16 * c.mt);
@@ -832,17 +889,17 @@ W4Cfg w4_pick(int M, int N, int K) {
   return c;
 }
 
-template <typename scalar_t, bool GROUPED>
+template <typename scalar_t, bool GROUPED, bool ZP = false>
 int w4_launch(const W4Params& p, const W4Cfg& cfg, hipStream_t stream) {
   const int C = p.N / 64;
   const int ncolwg = cfg.mt == 1 ? C : ceil_div(C, 4);
   dim3 grid(ncolwg, p.k_splits, ceil_div(p.M, 16 * cfg.mt));
   if (p.xcd_per > 0) grid = dim3(ceil_div(ncolwg, p.xcd_per) * 8, 1, grid.z);
-  if (cfg.mt == 8) w4a16_tall_kernel<scalar_t, GROUPED><<<grid, 256, 0, stream>>>(p);
-  else if (cfg.mt == 1 && cfg.nw == 8) w4a16_gemm_kernel<scalar_t, 1, 8, GROUPED, false><<<grid, 512, 0, stream>>>(p);
-  else if (cfg.mt == 1) w4a16_gemm_kernel<scalar_t, 1, 4, GROUPED, false><<<grid, 256, 0, stream>>>(p);
-  else if (cfg.mt == 2) w4a16_gemm_kernel<scalar_t, 2, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
-  else w4a16_gemm_kernel<scalar_t, 4, 4, GROUPED, true><<<grid, 256, 0, stream>>>(p);
+  if (!ZP && cfg.mt == 8) w4a16_tall_kernel<scalar_t, GROUPED><<<grid, 256, 0, stream>>>(p);  // (ZP: w4_pick never says 8)
+  else if (cfg.mt == 1 && cfg.nw == 8) w4a16_gemm_kernel<scalar_t, 1, 8, GROUPED, false, ZP><<<grid, 512, 0, stream>>>(p);
+  else if (cfg.mt == 1) w4a16_gemm_kernel<scalar_t, 1, 4, GROUPED, false, ZP><<<grid, 256, 0, stream>>>(p);
+  else if (cfg.mt == 2) w4a16_gemm_kernel<scalar_t, 2, 4, GROUPED, true, ZP><<<grid, 256, 0, stream>>>(p);
+  else w4a16_gemm_kernel<scalar_t, 4, 4, GROUPED, true, ZP><<<grid, 256, 0, stream>>>(p);
   NMX_LAUNCH_CHECK();
   return NMX_OK;
 }
@@ -893,10 +950,18 @@ int w8_launch(const W4Params& p, const W4Cfg& cfg, hipStream_t stream) {
   return NMX_OK;
 }
 
+// zeros_native != nullptr: the zero-point form (4 bits, fp16, one group per 128 k)
 int w4_common(int bits, const void* a, const int32_t* qweight_native, const void* scales_native, void* c, void* scratch,
               int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int defer,
-              int* splits_out, hipStream_t stream) {
+              int* splits_out, hipStream_t stream, const void* zeros_native = nullptr) {
   if (splits_out != nullptr) *splits_out = 1;
+  if (zeros_native != nullptr) {
+    NMX_CHECK(dtype == NMX_F16, NMX_ERR_UNSUPPORTED, "w4a16_zp_gemm only supports float16");
+    NMX_CHECK(nmx_awq_native_supported(size_n, size_k, num_groups), NMX_ERR_UNSUPPORTED,
+              "w4a16_zp_gemm: size_k = %d must be a multiple of 128, size_n = %d of 64, num_groups = %d size_k / 128", size_k, size_n,
+              num_groups);
+    NMX_CHECK((uintptr_t)zeros_native % 8 == 0, NMX_ERR_INVALID_ARG, "w4a16_zp_gemm: zeros_native must be 8-byte aligned");
+  }
   NMX_CHECK(dtype == NMX_F16 || dtype == NMX_BF16, NMX_ERR_UNSUPPORTED, "w4a16_gemm only supports bfloat16 and float16");
   NMX_CHECK(size_m >= 0 && size_n > 0 && size_k > 0, NMX_ERR_INVALID_ARG, "w4a16_gemm: size_m = %d, size_n = %d, size_k = %d", size_m,
             size_n, size_k);
@@ -911,18 +976,19 @@ int w4_common(int bits, const void* a, const int32_t* qweight_native, const void
                 ((uintptr_t)c % 8 == 0) && ((uintptr_t)scratch % 16 == 0),
             NMX_ERR_INVALID_ARG, "w4a16_gemm: operands must be 16-byte aligned");
   if (size_m == 0) return NMX_OK;
-  W4Cfg cfg = bits == 8 ? w8_pick(size_m, size_n, size_k) : w4_pick(size_m, size_n, size_k);
+  W4Cfg cfg = bits == 8 ? w8_pick(size_m, size_n, size_k) : w4_pick(size_m, size_n, size_k, zeros_native == nullptr);
   const int64_t slab = (int64_t)size_m * size_n * sizeof(float);
   if (scratch == nullptr) scratch_bytes = 0;
   if ((int64_t)cfg.splits * slab > scratch_bytes) cfg.splits = (int)std::max<int64_t>(1, scratch_bytes / slab);  // fewer splits, never past the scratch
   W4Params p;
   p.a = a; p.qw = qweight_native; p.scales = scales_native; p.c = c; p.partial = reinterpret_cast<float*>(scratch);
-  p.M = size_m; p.N = size_n; p.K = size_k; p.num_groups = num_groups; p.k_splits = cfg.splits;
+  p.M = size_m; p.N = size_n; p.K = size_k; p.num_groups = num_groups; p.k_splits = cfg.splits; p.zeros = zeros_native;
   const char* xs = nmx_tune(NMX_TUNE_GEMM_XCD_SPLIT);
   const bool xcd = (xs == nullptr || atoi(xs) != 0) && (cfg.splits == 2 || cfg.splits == 4 || cfg.splits == 8);
   p.xcd_per = xcd ? 8 / cfg.splits : 0;
   int rc;
-  if (bits == 8) {
+  if (zeros_native != nullptr) rc = w4_launch<f16, true, true>(p, cfg, stream);
+  else if (bits == 8) {
     if (dtype == NMX_F16) rc = num_groups > 1 ? w8_launch<f16, true>(p, cfg, stream) : w8_launch<f16, false>(p, cfg, stream);
     else rc = num_groups > 1 ? w8_launch<bf16, true>(p, cfg, stream) : w8_launch<bf16, false>(p, cfg, stream);
   } else if (dtype == NMX_F16) rc = num_groups > 1 ? w4_launch<f16, true>(p, cfg, stream) : w4_launch<f16, false>(p, cfg, stream);
@@ -990,6 +1056,64 @@ extern "C" int nmx_w4a16_gemm_deferred(const void* a, const int32_t* qweight_nat
   NMX_CHECK(splits_out != nullptr, NMX_ERR_INVALID_ARG, "splits_out is null");
   return w4_common(4, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 1, splits_out,
                    (hipStream_t)stream);
+}
+
+// ---- zero points (AWQ): the same entries with zeros_native; no 128-row form ----
+extern "C" int nmx_awq_native_supported(int size_n, int size_k, int num_groups) {
+  return nmx_w4a16_supported(size_n, size_k, num_groups, 4, 0) && num_groups == size_k / 128 ? 1 : 0;
+}
+
+extern "C" int nmx_awq_native_repack(const int32_t* qweight, const int32_t* qzeros, const void* scales, int32_t* qweight_native,
+                                     void* scales_native, void* zeros_native, int size_k, int size_n, int num_groups,
+                                     nmx_stream_t stream) {
+  NMX_CHECK(nmx_awq_native_supported(size_n, size_k, num_groups), NMX_ERR_UNSUPPORTED,
+            "awq_native_repack: size_k = %d must be a multiple of 128, size_n = %d of 64, num_groups = %d size_k / 128", size_k, size_n,
+            num_groups);
+  NMX_CHECK(qweight != nullptr && qzeros != nullptr && scales != nullptr && qweight_native != nullptr && scales_native != nullptr &&
+                zeros_native != nullptr && qweight != qweight_native && scales != scales_native,
+            NMX_ERR_INVALID_ARG, "awq_native_repack: null or aliased operand");
+  const int64_t blocks = (int64_t)(size_k / 128) * ceil_div(size_n / 64, 4);
+  NMX_CHECK(blocks < (1ll << 31), NMX_ERR_UNSUPPORTED, "awq_native_repack: weight too large");
+  awq_native_repack_kernel<<<(unsigned)blocks, 256, 0, (hipStream_t)stream>>>(
+      reinterpret_cast<const uint32_t*>(qweight), reinterpret_cast<const uint32_t*>(qzeros), reinterpret_cast<const uint16_t*>(scales),
+      reinterpret_cast<uint32_t*>(qweight_native), reinterpret_cast<uint16_t*>(scales_native), reinterpret_cast<uint16_t*>(zeros_native),
+      size_k, size_n);
+  NMX_LAUNCH_CHECK();
+  return NMX_OK;
+}
+
+extern "C" int nmx_w4a16_zp_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits) {
+  NMX_CHECK(mt != nullptr && nw != nullptr && splits != nullptr, NMX_ERR_INVALID_ARG, "w4a16_zp_gemm_plan: null output");
+  NMX_CHECK(size_m > 0 && size_n > 0 && size_k >= 128, NMX_ERR_INVALID_ARG, "w4a16_zp_gemm_plan: size_m = %d, size_n = %d, size_k = %d",
+            size_m, size_n, size_k);
+  const W4Cfg c = w4_pick(size_m, size_n, size_k, false);
+  *mt = c.mt;
+  *nw = c.nw;
+  *splits = c.splits;
+  return NMX_OK;
+}
+
+extern "C" int64_t nmx_w4a16_zp_gemm_scratch_bytes(int size_m, int size_n, int size_k) {
+  if (size_m <= 0 || size_n <= 0 || size_k < 128) return 0;
+  const int splits = w4_pick(size_m, size_n, size_k, false).splits;
+  return splits > 1 ? (int64_t)splits * size_m * size_n * sizeof(float) : 0;
+}
+
+extern "C" int nmx_w4a16_zp_gemm(const void* a, const int32_t* qweight_native, const void* scales_native, const void* zeros_native,
+                                 void* c, void* scratch, int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups,
+                                 int dtype, nmx_stream_t stream) {
+  NMX_CHECK(zeros_native != nullptr, NMX_ERR_INVALID_ARG, "w4a16_zp_gemm: null operand");
+  return w4_common(4, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 0, nullptr,
+                   (hipStream_t)stream, zeros_native);
+}
+
+extern "C" int nmx_w4a16_zp_gemm_deferred(const void* a, const int32_t* qweight_native, const void* scales_native,
+                                          const void* zeros_native, void* c, void* scratch, int64_t scratch_bytes, int size_m,
+                                          int size_n, int size_k, int num_groups, int dtype, int* splits_out, nmx_stream_t stream) {
+  NMX_CHECK(splits_out != nullptr, NMX_ERR_INVALID_ARG, "splits_out is null");
+  NMX_CHECK(zeros_native != nullptr, NMX_ERR_INVALID_ARG, "w4a16_zp_gemm: null operand");
+  return w4_common(4, a, qweight_native, scales_native, c, scratch, scratch_bytes, size_m, size_n, size_k, num_groups, dtype, 1, splits_out,
+                   (hipStream_t)stream, zeros_native);
 }
 
 // ---- 8 bits: the same entries on the 8-bit form of the layout ----

@@ -2,6 +2,7 @@
 from typing import Dict, Type
 
 from neuralmagic_vllm_amd.layers.quantization.awq import AWQConfig
+from neuralmagic_vllm_amd.layers.quantization.awq_native import AWQNativeConfig
 from neuralmagic_vllm_amd.layers.quantization.base_config import QuantizationConfig
 from neuralmagic_vllm_amd.layers.quantization.compressed_tensors import CompressedTensorsConfig
 from neuralmagic_vllm_amd.layers.quantization.fp8 import Fp8Config
@@ -19,6 +20,7 @@ QUANTIZATION_METHODS: Dict[str, Type[QuantizationConfig]] = {
     "gptq": GPTQConfig,
     "gptq_marlin": GPTQMarlinConfig,  # must stay before plain gptq in override order (reference comment, __init__.py:32-36)
     "marlin": MarlinConfig,
+    "awq_native": AWQNativeConfig,  # opt-in (native layout with zero points), chosen by name only; before gptq_native, which stays last
     "gptq_native": GPTQNativeConfig,  # opt-in (CDNA4-native W4A16 layout): last, its override only answers to its own name
 }
 

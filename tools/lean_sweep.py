@@ -8,7 +8,9 @@ cfg strings: "D:auto" = default dispatch, "L:nw,splits[,mt[,ws]]" = marlin_decod
 = w4a16_gemm_kernel, 8 = w4a16_tall_kernel), checked against the 64-row form "4,0,1" (the
 same random words mean other weights there than in Marlin's order); the line ends with the plan launched and its fp32 slab bytes.
 LEAN_SWEEP_BITS=8 runs every family on 8-bit weights (Marlin: num_bits = 8; "N:": the 8-bit form of the native layout), so
-LEAN_SWEEP_ONLY="D:auto;N:auto;D:auto;N:auto" times the Marlin and the native 8-bit path alternately in one call."""
+LEAN_SWEEP_ONLY="D:auto;N:auto;D:auto;N:auto" times the Marlin and the native 8-bit path alternately in one call.
+"A:auto" = awq_marlin_gemm and "Z:auto" / "Z:mt,nw,splits" = w4a16_gemm with zeros_native (NMX_W4A16), both on the same 32 random
+AWQ checkpoints (repacked once per shape for either path; "Z:" is checked against "A:"): LEAN_SWEEP_ONLY="A:auto;Z:auto;A:auto;Z:auto"."""
 import os
 import sys
 
@@ -32,11 +34,11 @@ def set_cfg(cfg):
     for k in ("NMX_GEMM_CFG", "NMX_GEMM_LEAN", "NMX_GEMM_LARGE", "NMX_GEMM_LARGE_NGRP", "NMX_GEMM_WIDE", "NMX_GEMM_DMA", "NMX_W4A16"):
         _lib.set_tuning(k, None)
     kind, val = cfg.split(":")
-    if kind == "N":  # w4a16_gemm_kernel "mt,nw,splits"
+    if kind in ("N", "Z"):  # w4a16_gemm_kernel "mt,nw,splits"
         if val != "auto":
             _lib.set_tuning("NMX_W4A16", val)
         return
-    if kind == "D":  # default dispatch, no override
+    if kind in ("D", "A"):  # default dispatch, no override
         return
     if kind == "X":  # marlin_dma_kernel with val K splits
         _lib.set_tuning("NMX_GEMM_DMA", val)
@@ -113,6 +115,7 @@ def main():
             continue
         ws = [(torch.randint(-2**31, 2**31 - 1, (K // 16, N * BITS // 2), dtype=torch.int32, device=dev, generator=g),
                (torch.rand(K // 128, N, device=dev, generator=g) * 0.004 + 0.002).half()) for _ in range(NL)]
+        awq = None  # (marlin triple, native triple) of 32 AWQ checkpoints, built at the first "A:" / "Z:" configuration
         for M in Ms:
             x = torch.randn(M, K, dtype=torch.float16, device=dev)
             set_cfg("S:auto")
@@ -130,6 +133,32 @@ def main():
                     us = time_graph(run_t) / NL
                     print(f"{'hipBLASLt-fp16':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {(2 * K * N + 2 * M * K + 2 * M * N) / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  (dense fp16 yardstick)", flush=True)
                     del dws
+                    continue
+                if cfg.startswith(("A:", "Z:")):
+                    if awq is None:
+                        awq = []
+                        for _, sc in ws:
+                            ck = [torch.randint(-2**31, 2**31 - 1, (rows, N // 8), dtype=torch.int32, device=dev, generator=g) for rows in (K, K // 128)]
+                            awq.append((ops.awq_marlin_repack(ck[0], ck[1], sc), ops.awq_native_repack(ck[0], ck[1], sc)))
+                    defer = os.environ.get("LEAN_SWEEP_DEFER") == "1"
+                    set_cfg(cfg)
+                    if cfg.startswith("A:"):
+                        gemm = ops.awq_marlin_gemm_deferred if defer else ops.awq_marlin_gemm
+                        call = lambda w: gemm(x, *w[0], M, N, K)  # noqa: E731
+                        tail = ""
+                    else:
+                        gemm = ops.w4a16_gemm_deferred if defer else ops.w4a16_gemm
+                        call = lambda w: gemm(x, w[1][0], w[1][1], M, N, K, zeros_native=w[1][2])  # noqa: E731
+                        aref = ops.awq_marlin_gemm(x, *awq[0][0], M, N, K).float()
+                        err = ((ops.w4a16_gemm(x, *awq[0][1][:2], M, N, K, zeros_native=awq[0][1][2]).float() - aref).abs().mean() / aref.abs().mean()).item()
+                        tail = f"relerr_vs_awq_marlin={err:.2e}  plan={ops.w4a16_gemm_plan(M, N, K, zeros_native=awq[0][1][2])}"
+
+                    def run_z():
+                        for w in awq:
+                            call(w)
+
+                    us = time_graph(run_z) / NL
+                    print(f"{'awq-marlin' if cfg[0] == 'A' else 'awq-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {by / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  {tail}", flush=True)
                     continue
                 if cfg.startswith("N:"):  # the native layout: the same 32 word tensors, viewed [K / 128, 16 N] (8 bits: 32 N)
                     try:
