@@ -410,6 +410,42 @@ int nmx_w8a16_gemm_deferred(const void* a, const int32_t* qweight_native, const 
                             int64_t scratch_bytes, int size_m, int size_n, int size_k, int num_groups, int dtype, int* splits_out,
                             nmx_stream_t stream);
 
+/* MXFP4 on the native layout (no reference counterpart): OCP MXFP4 weights AND dynamically quantised MXFP4
+ * activations on v_mfma_scale_f32_16x16x128_f8f6f4, fp32 accumulation, output in the activations' dtype (fp16 / bf16).
+ * size_k % 128 == 0 and size_n % 64 == 0: nmx_mxfp4_supported(). The numeric contract:
+ *   element  e2m1, codes 0..15 = +{0, 0.5, 1, 1.5, 2, 3, 4, 6}, then -{the same} (bit 3 = sign).
+ *   packing  two codes per byte, the low nibble is the even k.
+ *   scale    E8M0 byte b = 2^(b - 127), one per block = 32 consecutive k of one row. (255 = NaN is not produced, and not expected
+ *            in weight_scale.)
+ *   activation quantiser, per block with amax = max |x| (finite inputs only): e = clamp(floor(log2(amax)) - 2, -127, 127), e = -127
+ *            when amax = 0; scale byte = e + 127; element = x * 2^-e rounded to nearest even onto the e2m1 grid, saturating at +-6
+ *            (the OCP MX recipe); a negative x that rounds to zero keeps its sign (code 8). v_cvt_scalef32_pk_fp4_{f16,bf16} gives
+ *            exactly this. The value of a quantised activation is code * 2^e; products are exact, sums are fp32.
+ * The layout (the contract):
+ *   qweight_native  uint8 [size_k / 128, size_n / 16, 64 lanes, 16]: lane l = 16 g + i of tile (u, T) holds the 16 bytes of column
+ *     n = 16 T + i at k = 128 u + 32 g .. + 31, in checkpoint (natural) byte order: the lane's whole A operand for one MFMA, one
+ *     16-byte load; the lane's 32 values are one block and share one scale. size_k * size_n / 2 bytes.
+ *   scales_native   uint32 [size_k / 128, size_n / 64, 64 lanes]: byte t of lane l = 16 g + i of (u, c) is the E8M0 scale of column
+ *     n = 64 c + 16 t + i, block 4 u + g: one dword per lane serves the four tiles of a 64-column group, op_sel picks the byte.
+ * nmx_mxfp4_repack: checkpoint weight uint8 [size_n, size_k / 2] + weight_scale uint8 [size_n, size_k / 32] (AMD Quark
+ * w_mxfp4_a_mxfp4 exports) -> the native pair, one launch.
+ * nmx_mxfp4_quant: the activation quantiser as an op: input [size_m, size_k] fp16 / bf16 (size_k % 32 == 0) -> out_q uint8
+ * [size_m, size_k / 2] and out_scale uint8 [size_m, size_k / 32]. nmx_mxfp4_gemm quantises with the same code while it loads its
+ * rows: its result is, bit for bit, that of the MFMAs on nmx_mxfp4_quant's output.
+ * nmx_mxfp4_gemm: c [size_m, size_n] = Q(a) . W^T. size_m is free (row blocks of 64 above 64 rows). K splits write fp32 slabs
+ * [splits, size_m, size_n] to scratch (nmx_mxfp4_gemm_scratch_bytes; with less, fewer splits) and nmx_splitk_reduce finishes.
+ * nmx_mxfp4_gemm_plan: what the GEMM launches for a shape under the current NMX_MXFP4 = "mt,nw,splits" override (0 = default):
+ * *mt 16-row tiles per workgroup (1: activations quantised in registers, 2 / 4: once per workgroup into LDS), *nw waves of the
+ * mt = 1 form (4 / 8; 4 otherwise), *splits K splits. All entries only enqueue. */
+int nmx_mxfp4_supported(int size_n, int size_k);
+int nmx_mxfp4_repack(const uint8_t* weight, const uint8_t* weight_scale, void* qweight_native, uint32_t* scales_native, int size_k,
+                     int size_n, nmx_stream_t stream);
+int nmx_mxfp4_quant(uint8_t* out_q, uint8_t* out_scale, const void* input, int size_m, int size_k, int dtype, nmx_stream_t stream);
+int64_t nmx_mxfp4_gemm_scratch_bytes(int size_m, int size_n, int size_k);
+int nmx_mxfp4_gemm_plan(int size_m, int size_n, int size_k, int* mt, int* nw, int* splits);
+int nmx_mxfp4_gemm(const void* a, const void* qweight_native, const uint32_t* scales_native, void* c, void* scratch,
+                   int64_t scratch_bytes, int size_m, int size_n, int size_k, int dtype, nmx_stream_t stream);
+
 /* marlin_gemm (csrc/quantization/marlin/dense/marlin_cuda_kernel.cu:1045-1136): int4, fp16, groups of 128 or
  * channel-wise, weights Marlin-packed in the checkpoint. */
 int nmx_marlin_gemm(const void* a, const int32_t* b_q_weight, const void* b_scales, void* c,

@@ -1159,6 +1159,71 @@ def awq_native_repack(qweight: torch.Tensor, qzeros: torch.Tensor, scales: torch
     return out_q, out_s, out_z
 
 
+# ---------------------------------------------------------------------------------------------------------
+# MXFP4 on the native layout (extension; numeric and layout contract in include/nmx.h): e2m1 weights with one E8M0 scale per 32 k,
+# fp16 / bf16 activations quantised to MXFP4 per row and 32-k block inside the GEMM, fp32 accumulation. K % 128 == 0, N % 64 == 0.
+# ---------------------------------------------------------------------------------------------------------
+def mxfp4_supported(size_n: int, size_k: int) -> bool:
+    return bool(_lib.lib().nmx_mxfp4_supported(c_int(size_n), c_int(size_k)))
+
+
+def mxfp4_repack(weight: torch.Tensor, weight_scale: torch.Tensor):
+    """Checkpoint weight [N, K / 2] uint8 (two e2m1 codes per byte, low nibble = even k) + weight_scale [N, K / 32] uint8 (E8M0)
+    -> (qweight_native [K / 128, 64 N] uint8, scales_native [K / 128, N] int32: one dword per lane, N / 64 x 64 per unit)."""
+    _dev(weight)
+    if weight.dtype != torch.uint8 or weight_scale.dtype != torch.uint8 or weight.dim() != 2 or weight_scale.dim() != 2:
+        raise RuntimeError("mxfp4_repack: weight [N, K / 2] and weight_scale [N, K / 32] uint8 expected")
+    n, k = weight.shape[0], weight.shape[1] * 2
+    if weight_scale.shape != (n, k // 32) or k % 32 != 0:
+        raise RuntimeError(f"mxfp4_repack: weight_scale must be [N = {n}, K / 32 = {k // 32}], got {tuple(weight_scale.shape)}")
+    if not (weight.is_contiguous() and weight_scale.is_contiguous() and weight_scale.is_cuda):
+        raise RuntimeError("mxfp4_repack: contiguous GPU tensors expected")
+    out_q = torch.empty((max(k // 128, 0), n * 64), dtype=torch.uint8, device=weight.device)
+    out_s = torch.empty((max(k // 128, 0), n), dtype=torch.int32, device=weight.device)
+    _lib.check(_lib.lib().nmx_mxfp4_repack(_p(weight), _p(weight_scale), _p(out_q), _p(out_s), c_int(k), c_int(n), _stream(weight)))
+    return out_q, out_s
+
+
+def mxfp4_quant(input: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """The activation quantiser of the contract: input [M, K] fp16 / bf16, K % 32 == 0 -> (codes [M, K / 2] uint8, E8M0 scale bytes
+    [M, K / 32] uint8). mxfp4_gemm applies exactly this to its rows."""
+    _dev(input)
+    if input.dim() != 2 or not input.is_contiguous() or input.dtype not in (torch.float16, torch.bfloat16):
+        raise RuntimeError("mxfp4_quant: a contiguous [M, K] float16 / bfloat16 tensor expected")
+    m, k = input.shape
+    out_q = torch.empty((m, k // 2), dtype=torch.uint8, device=input.device)
+    out_s = torch.empty((m, k // 32), dtype=torch.uint8, device=input.device)
+    _lib.check(_lib.lib().nmx_mxfp4_quant(_p(out_q), _p(out_s), _p(input), c_int(m), c_int(k), c_int(_dt(input)), _stream(input)))
+    return out_q, out_s
+
+
+def mxfp4_gemm(a: torch.Tensor, qweight_native: torch.Tensor, scales_native: torch.Tensor, size_m: int, size_n: int,
+               size_k: int) -> torch.Tensor:
+    _dev(a)
+    if a.dim() != 2 or a.shape[0] != size_m or a.shape[1] != size_k or not a.is_contiguous():
+        raise RuntimeError(f"mxfp4_gemm: a must be a contiguous [size_m = {size_m}, size_k = {size_k}] tensor, got {tuple(a.shape)}")
+    if qweight_native.dtype != torch.uint8 or qweight_native.numel() * 2 != size_k * size_n or not qweight_native.is_contiguous():
+        raise RuntimeError(f"mxfp4_gemm: qweight_native must hold size_k * size_n / 2 = {size_k * size_n // 2} bytes")
+    if scales_native.dtype != torch.int32 or scales_native.numel() * 128 != size_k * size_n or not scales_native.is_contiguous():
+        raise RuntimeError(f"mxfp4_gemm: scales_native must hold size_k * size_n / 128 = {size_k * size_n // 128} int32 words")
+    if qweight_native.device != a.device or scales_native.device != a.device:
+        raise RuntimeError("mxfp4_gemm: all operands must be on the device of a")
+    c = torch.empty((size_m, size_n), dtype=a.dtype, device=a.device)
+    need = _lib.lib().nmx_mxfp4_gemm_scratch_bytes(c_int(size_m), c_int(size_n), c_int(size_k))
+    scratch = _get_scratch(a.device, int(need))
+    _lib.check(_lib.lib().nmx_mxfp4_gemm(_p(a), _p(qweight_native), _p(scales_native), _p(c), _p(scratch), c_i64(scratch.numel()),
+                                         c_int(size_m), c_int(size_n), c_int(size_k), c_int(_dt(a)), _stream(a)))
+    return c
+
+
+def mxfp4_gemm_plan(size_m: int, size_n: int, size_k: int):
+    """(mt, nw, splits) that mxfp4_gemm launches for this shape under the current NMX_MXFP4 override."""
+    mt, nw, splits = c_int(0), c_int(0), c_int(0)
+    _lib.check(_lib.lib().nmx_mxfp4_gemm_plan(c_int(size_m), c_int(size_n), c_int(size_k), ctypes.byref(mt), ctypes.byref(nw),
+                                              ctypes.byref(splits)))
+    return mt.value, nw.value, splits.value
+
+
 def gptq_gemm(a: torch.Tensor, b_q_weight: torch.Tensor, b_gptq_qzeros: torch.Tensor, b_gptq_scales: torch.Tensor,
               b_g_idx: torch.Tensor, use_exllama: bool, bit: int) -> torch.Tensor:
     # csrc/quantization/gptq/q_gemm.cu:1823-1848

@@ -11,6 +11,7 @@ from neuralmagic_vllm_amd.layers.quantization.gptq_marlin import GPTQMarlinConfi
 from neuralmagic_vllm_amd.layers.quantization.gptq_marlin_24 import GPTQMarlin24Config
 from neuralmagic_vllm_amd.layers.quantization.gptq_native import GPTQNativeConfig
 from neuralmagic_vllm_amd.layers.quantization.marlin import MarlinConfig
+from neuralmagic_vllm_amd.layers.quantization.mxfp4 import MXFP4Config
 
 QUANTIZATION_METHODS: Dict[str, Type[QuantizationConfig]] = {
     "awq": AWQConfig,
@@ -20,6 +21,7 @@ QUANTIZATION_METHODS: Dict[str, Type[QuantizationConfig]] = {
     "gptq": GPTQConfig,
     "gptq_marlin": GPTQMarlinConfig,  # must stay before plain gptq in override order (reference comment, __init__.py:32-36)
     "marlin": MarlinConfig,
+    "mxfp4": MXFP4Config,  # opt-in (MXFP4 weights and activations on the block-scaled fp4 MFMA), chosen by name only
     "awq_native": AWQNativeConfig,  # opt-in (native layout with zero points), chosen by name only; before gptq_native, which stays last
     "gptq_native": GPTQNativeConfig,  # opt-in (CDNA4-native W4A16 layout): last, its override only answers to its own name
 }

@@ -1,0 +1,83 @@
+"""OCP MXFP4 checkpoints (AMD Quark `w_mxfp4_a_mxfp4` exports) on the block-scaled fp4 MFMA of gfx950 (extension; no reference
+counterpart). Opt-in: `quantization="mxfp4"`.
+
+Weights are e2m1 with one E8M0 scale per 32 k: `weight` uint8 [N, K / 2], `weight_scale` uint8 [N, K / 32]. Activations stay
+fp16 / bf16 up to the GEMM, which quantises them to MXFP4 per row and 32-k block as it loads them (the contract in include/nmx.h).
+The first `apply` repacks the pair with `ops.mxfp4_repack` and drops the checkpoint tensors. There is no other fp4 path to fall
+back to: `create_weights` refuses a shard the kernel does not take (K % 128 != 0 or N % 64 != 0)."""
+from typing import Any, Dict, List, Optional
+
+import torch
+from torch.nn.parameter import Parameter
+
+from neuralmagic_vllm_amd import _custom_ops as ops
+from neuralmagic_vllm_amd.layers.quantization.base_config import LinearMethodBase, QuantizationConfig, set_weight_attrs
+
+MX_BLOCK = 32
+
+
+class MXFP4Config(QuantizationConfig):
+
+    def __init__(self, block_size: int = MX_BLOCK):
+        if block_size != MX_BLOCK:
+            raise ValueError(f"mxfp4: the MX block is {MX_BLOCK} k-values, the checkpoint says {block_size}")
+        self.block_size = block_size
+
+    def __repr__(self) -> str:
+        return f"MXFP4Config(block_size={self.block_size})"
+
+    def get_name(self) -> str:
+        return "mxfp4"
+
+    def get_supported_act_dtypes(self) -> List[torch.dtype]:
+        return [torch.half, torch.bfloat16]
+
+    @staticmethod
+    def get_config_filenames() -> List[str]:
+        return ["quant_config.json", "quantize_config.json"]
+
+    @classmethod
+    def from_config(cls, config: Dict[str, Any]) -> "MXFP4Config":
+        return cls(cls.get_from_keys_or(config, ["block_size", "group_size"], MX_BLOCK))
+
+    def get_quant_method(self, layer: torch.nn.Module) -> Optional["MXFP4LinearMethod"]:
+        return MXFP4LinearMethod(self)
+
+
+class MXFP4LinearMethod(LinearMethodBase):
+
+    def __init__(self, quant_config: MXFP4Config):
+        self.quant_config = quant_config
+
+    def create_weights(self, layer: torch.nn.Module, input_size_per_partition: int, output_partition_sizes: List[int],
+                       input_size: int, output_size: int, params_dtype: torch.dtype, **extra_weight_attrs):
+        out_pp = sum(output_partition_sizes)
+        if input_size_per_partition % 128 != 0 or out_pp % 64 != 0:
+            raise ValueError(f"mxfp4: a shard with K = {input_size_per_partition}, N = {out_pp} is not supported: K must be a multiple "
+                             "of 128 and N of 64 (this can be caused by too large tensor parallel size); there is no other fp4 path")
+        weight = Parameter(torch.empty(out_pp, input_size_per_partition // 2, dtype=torch.uint8), requires_grad=False)
+        set_weight_attrs(weight, {"input_dim": 1, "output_dim": 0, "packed_dim": 1, "pack_factor": 2})
+        weight_scale = Parameter(torch.empty(out_pp, input_size_per_partition // MX_BLOCK, dtype=torch.uint8), requires_grad=False)
+        set_weight_attrs(weight_scale, {"input_dim": 1, "output_dim": 0, "packed_dim": 1, "pack_factor": MX_BLOCK})
+        for name, prm in (("weight", weight), ("weight_scale", weight_scale)):
+            layer.register_parameter(name, prm)
+            set_weight_attrs(prm, extra_weight_attrs)
+        layer.input_size_per_partition = input_size_per_partition
+        layer.output_size_per_partition = out_pp
+        layer.mxfp4_native = None
+
+    def process_weights_after_loading(self, layer: torch.nn.Module) -> None:
+        if layer.mxfp4_native is not None:
+            return
+        layer.mxfp4_native = ops.mxfp4_repack(layer.weight.data.contiguous(), layer.weight_scale.data.contiguous())
+        for name in ("weight", "weight_scale"):  # the checkpoint tensors are dropped
+            getattr(layer, name).data = torch.empty(0, dtype=torch.uint8, device=layer.mxfp4_native[0].device)
+
+    def apply(self, layer: torch.nn.Module, x: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+        self.process_weights_after_loading(layer)
+        k, n = layer.input_size_per_partition, layer.output_size_per_partition
+        reshaped_x = x.reshape(-1, x.shape[-1]).contiguous()
+        out = ops.mxfp4_gemm(reshaped_x, *layer.mxfp4_native, reshaped_x.shape[0], n, k)
+        if bias is not None:
+            out.add_(bias)
+        return out.reshape(x.shape[:-1] + (n, ))

@@ -10,7 +10,10 @@ same random words mean other weights there than in Marlin's order); the line end
 LEAN_SWEEP_BITS=8 runs every family on 8-bit weights (Marlin: num_bits = 8; "N:": the 8-bit form of the native layout), so
 LEAN_SWEEP_ONLY="D:auto;N:auto;D:auto;N:auto" times the Marlin and the native 8-bit path alternately in one call.
 "A:auto" = awq_marlin_gemm and "Z:auto" / "Z:mt,nw,splits" = w4a16_gemm with zeros_native (NMX_W4A16), both on the same 32 random
-AWQ checkpoints (repacked once per shape for either path; "Z:" is checked against "A:"): LEAN_SWEEP_ONLY="A:auto;Z:auto;A:auto;Z:auto"."""
+AWQ checkpoints (repacked once per shape for either path; "Z:" is checked against "A:"): LEAN_SWEEP_ONLY="A:auto;Z:auto;A:auto;Z:auto".
+"F:auto" / "F:mt,nw,splits" = mxfp4_gemm (NMX_MXFP4) on 32 random MXFP4 weights of the shape, checked against its 64-row form "4,0,1";
+its line counts the MXFP4 bytes (K N / 2 codes + K N / 32 scale bytes) and ends with their share of an 8 TB/s stream:
+LEAN_SWEEP_ONLY="N:auto;F:auto;N:auto;F:auto" times it against the int4 native path alternately in one call."""
 import os
 import sys
 
@@ -31,9 +34,13 @@ dev = "cuda:0"
 
 def set_cfg(cfg):
     from neuralmagic_vllm_amd import _lib
-    for k in ("NMX_GEMM_CFG", "NMX_GEMM_LEAN", "NMX_GEMM_LARGE", "NMX_GEMM_LARGE_NGRP", "NMX_GEMM_WIDE", "NMX_GEMM_DMA", "NMX_W4A16"):
+    for k in ("NMX_GEMM_CFG", "NMX_GEMM_LEAN", "NMX_GEMM_LARGE", "NMX_GEMM_LARGE_NGRP", "NMX_GEMM_WIDE", "NMX_GEMM_DMA", "NMX_W4A16", "NMX_MXFP4"):
         _lib.set_tuning(k, None)
     kind, val = cfg.split(":")
+    if kind == "F":  # mxfp4_gemm_kernel "mt,nw,splits"
+        if val != "auto":
+            _lib.set_tuning("NMX_MXFP4", val)
+        return
     if kind in ("N", "Z"):  # w4a16_gemm_kernel "mt,nw,splits"
         if val != "auto":
             _lib.set_tuning("NMX_W4A16", val)
@@ -115,6 +122,7 @@ def main():
             continue
         ws = [(torch.randint(-2**31, 2**31 - 1, (K // 16, N * BITS // 2), dtype=torch.int32, device=dev, generator=g),
                (torch.rand(K // 128, N, device=dev, generator=g) * 0.004 + 0.002).half()) for _ in range(NL)]
+        fp4 = None  # 32 repacked MXFP4 weights, built at the first "F:" configuration
         awq = None  # (marlin triple, native triple) of 32 AWQ checkpoints, built at the first "A:" / "Z:" configuration
         for M in Ms:
             x = torch.randn(M, K, dtype=torch.float16, device=dev)
@@ -133,6 +141,23 @@ def main():
                     us = time_graph(run_t) / NL
                     print(f"{'hipBLASLt-fp16':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {(2 * K * N + 2 * M * K + 2 * M * N) / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  (dense fp16 yardstick)", flush=True)
                     del dws
+                    continue
+                if cfg.startswith("F:"):
+                    if fp4 is None:
+                        fp4 = [ops.mxfp4_repack(torch.randint(0, 256, (N, K // 2), dtype=torch.uint8, device=dev, generator=g),
+                                                torch.randint(118, 131, (N, K // 32), dtype=torch.uint8, device=dev, generator=g)) for _ in range(NL)]
+                    set_cfg("F:4,0,1")
+                    fref = ops.mxfp4_gemm(x, *fp4[0], M, N, K).float()
+                    set_cfg(cfg)
+                    err = ((ops.mxfp4_gemm(x, *fp4[0], M, N, K).float() - fref).abs().mean() / fref.abs().mean()).item()
+
+                    def run_f():
+                        for w in fp4:
+                            ops.mxfp4_gemm(x, w[0], w[1], M, N, K)
+
+                    us = time_graph(run_f) / NL
+                    fby = K * N // 2 + K * N // 32 + 2 * M * K + 2 * M * N
+                    print(f"{'mxfp4-native':18} {name:8} M={M:4d} {cfg:12} {us:7.2f} us  {fby / us / 1e3:7.0f} GB/s  {2.0 * M * K * N / us / 1e6:7.1f} TFLOP/s  relerr_vs_mt4={err:.2e}  plan={ops.mxfp4_gemm_plan(M, N, K)}  stream_share={(K * N // 2 + K * N // 32) / 8e6 / us:.2f}", flush=True)
                     continue
                 if cfg.startswith(("A:", "Z:")):
                     if awq is None:
