@@ -623,6 +623,34 @@ int nmx_moe_w4a16_mm(void* out, const void* a, const int32_t* qweight_native, co
 int64_t nmx_moe_w4a16_mm_scratch_bytes(int num_valid, int n, int k, int num_experts, int block_rows);
 int nmx_moe_w4a16_mm_plan(int num_valid, int n, int k, int num_experts, int block_rows, int* splits);
 
+/* MXFP4 mixture-of-experts: the grouped GEMM on the block-scaled fp4 MFMA (extension; elements, scales and the
+ * native layout are those of "MXFP4 on the native layout" above). qweight_native uint8 [num_experts, k / 128, 64 n] and
+ * scales_native int32 [num_experts, k / 128, n] are the outputs of nmx_mxfp4_repack of every expert, stacked; k % 128 == 0,
+ * n % 64 == 0. The activations arrive QUANTISED, in the format nmx_mxfp4_quant writes: a_q uint8 [a_rows, k / 2] codes and a_scale
+ * uint8 [a_rows, k / 32] E8M0 bytes (a token row feeds topk experts times every column workgroup; it is quantised once).
+ *   out[id, :] = cast((A[id / a_row_div, :] . W_e^T) * [topk_weights[id]]),  A and W_e as dequantised: code * 2^(byte - 127)
+ * for every id of every block of `block_rows` (16, 32 or 64) entries of sorted_token_ids (entries >= num_valid are padding),
+ * e = expert_ids[block]. Products are exact, sums are fp32, the routing weight (topk_weights may be null) multiplies the fp32 sum
+ * before the cast to `dtype` (fp16 / bf16: the type of out only). By the bit-identity contract of nmx_mxfp4_gemm, a one-expert call
+ * on nmx_mxfp4_quant(x) is that GEMM on x up to the order of the fp32 sums. out [num_valid, n]; max_blocks = entries of
+ * expert_ids; blocks past num_tokens_post_padded[0] do nothing. With K splits (nmx_moe_mxfp4_mm_plan; chosen from the arguments
+ * alone by the rule of nmx_moe_w4a16_mm_plan, NMX_MOE_MXFP4 = "1" / "2" / "4" forces them) the fp32 partial sums go through
+ * `scratch` (nmx_moe_mxfp4_mm_scratch_bytes; with less, fewer splits) and nmx_splitk_reduce writes out. Any other block_rows, an
+ * unsupported shape, or one expert's weights, a_q or out beyond the 2 GiB of a 32-bit buffer offset return an error and launch
+ * nothing. Nothing is read on the host: capturable.
+ * nmx_silu_and_mul_mxfp4_quant: x [rows, 2 inter] fp16 / bf16 (gate | up, inter % 32 == 0) -> out_q uint8 [rows, inter / 2] and
+ * out_scale uint8 [rows, inter / 32]: bit for bit nmx_mxfp4_quant of nmx_silu_and_mul(x) (silu in fp32 rounded to dtype, the
+ * product rounded to dtype, then the quantiser), one launch. All entries only enqueue. */
+int nmx_moe_mxfp4_mm(void* out, const uint8_t* a_q, const uint8_t* a_scale, const uint8_t* qweight_native,
+                     const int32_t* scales_native, const float* topk_weights, const int32_t* sorted_token_ids,
+                     const int32_t* expert_ids, const int32_t* num_tokens_post_padded, void* scratch, int64_t scratch_bytes,
+                     int num_valid, int a_rows, int a_row_div, int n, int k, int num_experts, int block_rows, int max_blocks,
+                     int dtype, nmx_stream_t stream);
+int64_t nmx_moe_mxfp4_mm_scratch_bytes(int num_valid, int n, int k, int num_experts, int block_rows);
+int nmx_moe_mxfp4_mm_plan(int num_valid, int n, int k, int num_experts, int block_rows, int* splits);
+int nmx_silu_and_mul_mxfp4_quant(uint8_t* out_q, uint8_t* out_scale, const void* x, int rows, int inter, int dtype,
+                                 nmx_stream_t stream);
+
 /*
  * All-reduce over the xGMI mesh for decode-sized messages. Replaces the `_C_custom_ar` ops of the reference
  * (csrc/custom_all_reduce.cu: meta_size, init_custom_ar, register_buffer, should_custom_ar, all_reduce_reg, dispose; kernels

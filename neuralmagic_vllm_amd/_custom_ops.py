@@ -1554,6 +1554,69 @@ def moe_w4a16_mm_plan(num_valid: int, size_n: int, size_k: int, num_experts: int
     return splits.value
 
 
+def moe_mxfp4_mm(out: torch.Tensor, a_q: torch.Tensor, a_scale: torch.Tensor, qweight_native: torch.Tensor,
+                 scales_native: torch.Tensor, topk_weights: Optional[torch.Tensor], sorted_token_ids: torch.Tensor,
+                 expert_ids: torch.Tensor, num_tokens_post_padded: torch.Tensor, a_row_div: int, block_rows: int) -> None:
+    """Grouped MXFP4 GEMM over the expert-sorted (token, k) pairs on the block-scaled fp4 MFMA (extension; include/nmx.h):
+    out[id] = (A[id // a_row_div] @ W[expert].T) * [topk_weights[id]] on the dequantised values, fp32 sums.
+    a_q [rows, K / 2] and a_scale [rows, K / 32] uint8 (the outputs of mxfp4_quant), qweight_native [E, K / 128, 64 N] uint8 and
+    scales_native [E, K / 128, N] int32 (every expert's mxfp4_repack, stacked), out [num_valid, N] fp16 / bf16.
+    block_rows 16, 32 or 64. No host reads: graph-capturable."""
+    _dev(a_q)
+    if out.dtype not in (torch.float16, torch.bfloat16) or out.dim() != 2 or not out.is_contiguous():
+        raise RuntimeError("moe_mxfp4_mm: out must be a contiguous [num_valid, N] float16 / bfloat16 tensor")
+    if a_q.dtype != torch.uint8 or a_scale.dtype != torch.uint8 or a_q.dim() != 2 or a_scale.dim() != 2 or \
+            not (a_q.is_contiguous() and a_scale.is_contiguous()):
+        raise RuntimeError("moe_mxfp4_mm: a_q [rows, K / 2] and a_scale [rows, K / 32] must be contiguous uint8 tensors")
+    if qweight_native.dtype != torch.uint8 or scales_native.dtype != torch.int32 or qweight_native.dim() != 3 or scales_native.dim() != 3 or \
+            not (qweight_native.is_contiguous() and scales_native.is_contiguous()):
+        raise RuntimeError("moe_mxfp4_mm: qweight_native [E, K / 128, 64 N] uint8 and scales_native [E, K / 128, N] int32, contiguous")
+    e, units, n = scales_native.shape
+    k = 128 * units
+    if out.shape[1] != n or tuple(qweight_native.shape) != (e, units, 64 * n) or a_q.shape[1] * 2 != k or \
+            tuple(a_scale.shape) != (a_q.shape[0], k // 32):
+        raise RuntimeError(f"moe_mxfp4_mm: for E = {e}, K = {k}, N = {n}: qweight_native {tuple(qweight_native.shape)}, a_q "
+                           f"{tuple(a_q.shape)}, a_scale {tuple(a_scale.shape)} or out {tuple(out.shape)} do not fit")
+    for t in (sorted_token_ids, expert_ids, num_tokens_post_padded):
+        if t.dtype != torch.int32 or not t.is_contiguous():
+            raise RuntimeError("moe_mxfp4_mm: index tensors must be contiguous int32")
+    tw = None
+    if topk_weights is not None:
+        tw = topk_weights.reshape(-1)
+        if tw.dtype != torch.float32 or not tw.is_contiguous() or tw.numel() != out.shape[0]:
+            raise RuntimeError("moe_mxfp4_mm: topk_weights must be float32 with one entry per output row")
+    if any(t.device != a_q.device for t in (out, a_scale, qweight_native, scales_native, sorted_token_ids, expert_ids, num_tokens_post_padded)):
+        raise RuntimeError("moe_mxfp4_mm: all operands must be on the device of a_q")
+    lib = _lib.lib()
+    need = lib.nmx_moe_mxfp4_mm_scratch_bytes(c_int(out.shape[0]), c_int(n), c_int(k), c_int(e), c_int(block_rows))
+    scratch = _get_scratch(a_q.device, int(need))
+    _lib.check(lib.nmx_moe_mxfp4_mm(
+        _p(out), _p(a_q), _p(a_scale), _p(qweight_native), _p(scales_native), _p(tw), _p(sorted_token_ids), _p(expert_ids),
+        _p(num_tokens_post_padded), _p(scratch), c_i64(scratch.numel()), c_int(out.shape[0]), c_int(a_q.shape[0]), c_int(a_row_div),
+        c_int(n), c_int(k), c_int(e), c_int(block_rows), c_int(expert_ids.numel()), c_int(_dt(out)), _stream(a_q)))
+
+
+def moe_mxfp4_mm_plan(num_valid: int, size_n: int, size_k: int, num_experts: int, block_rows: int) -> int:
+    """K splits that moe_mxfp4_mm launches for this call under the current NMX_MOE_MXFP4 override."""
+    splits = c_int(0)
+    _lib.check(_lib.lib().nmx_moe_mxfp4_mm_plan(c_int(num_valid), c_int(size_n), c_int(size_k), c_int(num_experts), c_int(block_rows),
+                                                ctypes.byref(splits)))
+    return splits.value
+
+
+def silu_and_mul_mxfp4_quant(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """silu_and_mul fused with the MXFP4 activation quantiser: x [rows, 2 I] fp16 / bf16 (gate | up) -> (codes [rows, I / 2] uint8,
+    E8M0 scale bytes [rows, I / 32] uint8), bit for bit mxfp4_quant of silu_and_mul's output."""
+    _dev(x)
+    if x.dtype not in (torch.float16, torch.bfloat16) or x.dim() != 2 or not x.is_contiguous() or x.shape[1] % 64 != 0:
+        raise RuntimeError("silu_and_mul_mxfp4_quant: a contiguous [rows, 2 I] float16 / bfloat16 tensor with I % 32 == 0 expected")
+    rows, inter = x.shape[0], x.shape[1] // 2
+    out_q = torch.empty(rows, inter // 2, dtype=torch.uint8, device=x.device)
+    out_s = torch.empty(rows, inter // 32, dtype=torch.uint8, device=x.device)
+    _lib.check(_lib.lib().nmx_silu_and_mul_mxfp4_quant(_p(out_q), _p(out_s), _p(x), c_int(rows), c_int(inter), c_int(_dt(x)), _stream(x)))
+    return out_q, out_s
+
+
 def topk_softmax(topk_weights: torch.Tensor, topk_ids: torch.Tensor, token_expert_indicies: torch.Tensor,
                  gating_output: torch.Tensor) -> None:
     _dev(gating_output)

@@ -28,10 +28,11 @@ def lib() -> ctypes.CDLL:
         _lib.nmx_version.restype = ctypes.c_char_p
         for fn in ("nmx_marlin_gemm_scratch_bytes", "nmx_zp_gemm_scratch_bytes", "nmx_scaled_mm_scratch_bytes",
                    "nmx_w4a16_gemm_scratch_bytes", "nmx_w8a16_gemm_scratch_bytes", "nmx_moe_w4a16_mm_scratch_bytes",
-                   "nmx_w4a16_zp_gemm_scratch_bytes", "nmx_mxfp4_gemm_scratch_bytes"):
+                   "nmx_w4a16_zp_gemm_scratch_bytes", "nmx_mxfp4_gemm_scratch_bytes", "nmx_moe_mxfp4_mm_scratch_bytes"):
             getattr(_lib, fn).restype = ctypes.c_int64
-        _lib.nmx_moe_w4a16_mm_scratch_bytes.argtypes = [ctypes.c_int] * 5
-        _lib.nmx_moe_w4a16_mm_plan.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]
+        for fn in ("nmx_moe_w4a16_mm", "nmx_moe_mxfp4_mm"):
+            getattr(_lib, fn + "_scratch_bytes").argtypes = [ctypes.c_int] * 5
+            getattr(_lib, fn + "_plan").argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]
         _lib.nmx_tuning_set.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
         for fn in ("nmx_w4a16_gemm_plan", "nmx_w8a16_gemm_plan", "nmx_w4a16_zp_gemm_plan", "nmx_mxfp4_gemm_plan"):
             getattr(_lib, fn).argtypes = [ctypes.c_int] * 3 + [ctypes.POINTER(ctypes.c_int)] * 3

@@ -147,6 +147,47 @@ def fused_experts_w4a16(hidden_states: torch.Tensor, w13_q: torch.Tensor, w13_s:
     return out
 
 
+def mxfp4_block_rows(numel: int, num_experts: int) -> int:
+    """Rows per block of the grouped MXFP4 GEMM. Measured on Mixtral-8x7B shapes (tools/moe_mxfp4_ab.py): 16-row
+    blocks are ahead at 2 pairs (42.9 vs 50.5 us), 64-row blocks from 4 pairs per expert on (126 vs 132 us at 32 pairs, 162 vs 200
+    at 128, 230 vs 634 at 512) - earlier than the siblings' 16 E, because a staged block costs no conversion here. Between 2 and 32
+    pairs nothing is measured; 32-row blocks were never ahead of both."""
+    return 16 if numel < 4 * num_experts else 64
+
+
+def fused_experts_mxfp4(hidden_states: torch.Tensor, w13_q: torch.Tensor, w13_s: torch.Tensor, w2_q: torch.Tensor,
+                        w2_s: torch.Tensor, topk_weights: torch.Tensor, topk_ids: torch.Tensor, inplace: bool = False) -> torch.Tensor:
+    """fused_experts on MXFP4 experts held in the native layout of the fp4 MFMA (extension; no reference counterpart): align ->
+    mxfp4_quant (every token row once) -> grouped GEMM (gate | up) -> silu_and_mul fused with the quantiser -> grouped GEMM with the
+    routing weight -> sum over k. w13_q [E, H / 128, 64 * 2 I] uint8 and w13_s [E, H / 128, 2 I] int32 (gate | up), w2_q
+    [E, I / 128, 64 H] and w2_s [E, I / 128, H]: every expert's `mxfp4_repack`, stacked. Every step is a device launch:
+    graph-capturable."""
+    assert topk_weights.shape == topk_ids.shape, "topk shape mismatch"
+    assert hidden_states.is_contiguous() and hidden_states.dtype in (torch.float16, torch.bfloat16)
+    m, k = hidden_states.shape
+    e, _, n2 = w13_s.shape
+    h = w2_s.shape[2]
+    assert w13_q.shape[1] * 128 == k and h == k and w2_q.shape[1] * 128 == n2 // 2, "Hidden / intermediate size mismatch"
+    topk = topk_ids.shape[1]
+    dev, dt = hidden_states.device, hidden_states.dtype
+    numel = m * topk
+    block = mxfp4_block_rows(numel, e)
+    max_sorted = numel + e * (block - 1)
+    sorted_ids = torch.empty(max_sorted, dtype=torch.int32, device=dev)
+    expert_ids = torch.empty((max_sorted + block - 1) // block, dtype=torch.int32, device=dev)
+    post_pad = torch.empty(1, dtype=torch.int32, device=dev)
+    ops.moe_align_block_size(topk_ids.contiguous(), e, block, sorted_ids, expert_ids, post_pad)
+    x_q, x_s = ops.mxfp4_quant(hidden_states)
+    gate_up = torch.empty(numel, n2, dtype=dt, device=dev)
+    ops.moe_mxfp4_mm(gate_up, x_q, x_s, w13_q, w13_s, None, sorted_ids, expert_ids, post_pad, topk, block)
+    i_q, i_s = ops.silu_and_mul_mxfp4_quant(gate_up)
+    out_rows = torch.empty(numel, h, dtype=dt, device=dev)
+    ops.moe_mxfp4_mm(out_rows, i_q, i_s, w2_q, w2_s, topk_weights.float().contiguous(), sorted_ids, expert_ids, post_pad, 1, block)
+    out = hidden_states if inplace else torch.empty_like(hidden_states)
+    torch.sum(out_rows.view(m, topk, h), dim=1, out=out)  # moe_sum
+    return out
+
+
 def _fused_experts_fp8(hidden_states, w1, w2, topk_weights, topk_ids, inplace, w1_scale, w2_scale, a1_scale, a2_scale):
     """fused_experts with use_fp8 (fused_moe.py:402-511): align -> quantise -> grouped GEMM (gate | up) -> silu_and_mul ->
     quantise -> grouped GEMM with the routing weight -> sum over k. Every step is a device launch."""
